@@ -7,6 +7,12 @@ field, 6 cascade levels, blur + copy-back, merge + copy-back) over a synthetic p
 scene already resident in HBM (the reference's demo scene scaled to 4096^2).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--size 4096] [--cascades 6]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line of the headline figure.
+--dump-outputs DIR writes what the last timed step left a caller (distRT, the final GI, colorRT) as
+DIR/<name>.npy.  --full adds what takes runs of its own: the per-level times and the gather / VALU
+rooflines priced on them, the input costs and the CPU baseline.
 
 Multi-GPU: one process per GPU (torch.distributed.run), each rank renders its own scene
 (the path has no exchange step at this size: replicas, "scaling": "weak"); rank 0 prints
@@ -192,6 +198,30 @@ def input_costs(ctx, W, H, color, emis, reps=5):
     upload_ms = (time.perf_counter() - t0) * 1e3 / reps
     return {"device_paint_ms": round(paint_ms, 3), "host_upload_ms": round(upload_ms, 3),
             "note": "both input textures per frame; not part of value"}
+
+
+# What a caller of DoRC2DGI() receives: the distance field, the final GI (blurred, blended) and the
+# merged colorRT.  --dump-outputs writes them as float32 texels, all of them while the three arrays
+# fit DUMP_BUDGET_BYTES together, else the same seeded sample of texels of each.
+DUMP_NAMES = ("dist", "final_gi", "color")
+DUMP_BUDGET_BYTES = 48 << 20
+DUMP_SEED = 20240607
+
+
+def dump_outputs(ctx, out_dir, rank=0):
+    """DIR/<name>.npy (rank 0; DIR/<name>.rank<r>.npy on the others) of the frame the context last ran:
+    (rows, width, 4) float32 when whole, (texels, 4) in ascending texel order when sampled."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // len(DUMP_NAMES) // 16  # RGBA32F texels per array
+    for name in DUMP_NAMES:
+        a = np.ascontiguousarray(ctx.download(name), np.float32)
+        texels = a.shape[0] * a.shape[1]
+        if texels > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(texels, cap, replace=False))
+            a = a.reshape(texels, 4)[idx]
+        np.save(os.path.join(out_dir, name + (f".rank{rank}" if rank else "") + ".npy"), a)
 
 
 def sweep_rc(ctx, N, steps, rounds=3):
@@ -529,7 +559,13 @@ def main():
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--cascades", type=int, default=6)
     ap.add_argument("--ray-range", type=float, default=2.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (dist, final_gi, color) as "
+                         "DIR/<name>.npy (float32; a fixed seeded sample of texels at large sizes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also measure what takes runs of its own: per-level "
+                         "times and the gather / VALU rooflines, input costs, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--sweep-rc", action="store_true",
                     help="time every RC tile variant per level (interleaved rounds) instead of the bench line")
@@ -561,6 +597,9 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="no GPU work: bring up the ranks, print the world size the line would carry")
     a = ap.parse_args()
+    if a.dump_outputs and (a.batch or a.mode == "strips" or a.sweep_rc or a.launch_check):
+        ap.error("--dump-outputs writes the one-context frame's outputs (not with --batch, --mode strips, "
+                 "--sweep-rc or --launch-check)")
 
     # --gpus N is the rank count.  Without a torch.distributed.run environment, spawn it here as a
     # child process -- before anything touches the GPU -- and exit with its code; inside one, a
@@ -667,14 +706,17 @@ def main():
     torch.cuda.synchronize()
     rdist.barrier()
     wall = time.perf_counter() - t0
-    # per-level breakdown (and the gather / VALU rooflines priced on it): further frames with an
+    if a.dump_outputs:  # what the last timed step left, before anything else runs on the context
+        dump_outputs(ctx, a.dump_outputs, rank)
+    # --full: per-level breakdown (and the gather / VALU rooflines priced on it): further frames with an
     # event around every level, after the timed region
-    ctx.set_timing(True)
     lvl_steps = max(1, min(a.steps, 20))
-    for _ in range(lvl_steps):
-        ctx.do_rc2dgi()
-        lvl_ms += np.array(ctx.pass_times(levels=N)["levels"])
-    lvl_ms *= a.steps / lvl_steps  # (as a sum over a.steps frames, like rc_ms)
+    if a.full:
+        ctx.set_timing(True)
+        for _ in range(lvl_steps):
+            ctx.do_rc2dgi()
+            lvl_ms += np.array(ctx.pass_times(levels=N)["levels"])
+        lvl_ms *= a.steps / lvl_steps  # (as a sum over a.steps frames, like rc_ms)
     t_rc, t_tot, wall = rdist.max_over_ranks([sum(rc_ms), sum(tot_ms), wall], device="cuda")
     units = CW * CH * N * a.steps * world
     value = units / (t_rc / 1e3) / 1e6
@@ -690,6 +732,7 @@ def main():
     chain = bool(tuning_or_none(ctx, "rc_chain"))
     if rec is not None and not chain:
         traffic = rec.get("hbm_bytes_per_launch")
+    if rec is not None and not chain and a.full:
         gather = gather_roofline(rec, N, lvl_ms / a.steps)
         mixp = os.path.join(ROOT, "profiles", "rc_isa_mix.json")
         mix = json.load(open(mixp)) if os.path.exists(mixp) else None
@@ -738,12 +781,15 @@ def main():
                      "kernel": "k_rc_level", "bytes_per_launch": bytes_launch,
                      "avg_launch_ms": round(avg_launch_s * 1e3, 5)},
     }
+    if not a.full:  # a plain run times no per-level frames
+        del line["rc_level_ms"], line["rc_level_timing"]
     if gather:
         line["gather_roofline"] = gather
     if valu:
         line["valu_roofline"] = valu
-    line["inputs"] = input_costs(ctx, W, H, color, emis)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:  # the CPU leg: rank 0 at N=1 only
+    if a.full:
+        line["inputs"] = input_costs(ctx, W, H, color, emis)
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:  # the CPU leg: rank 0 at N=1 only
         line["cpu_baseline"] = cpu_baseline(W, H, N, a.ray_range, a.cpu_budget)
     if rank == 0:
         print(json.dumps(line), flush=True)

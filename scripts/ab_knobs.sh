@@ -3,6 +3,7 @@
 # (each line: setting, value, RC ms, per-level ms, full frame ms).  CFGS: settings, commas between
 # the KEY=VALUE pairs of one setting, "base" for none.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
+BENCH_ARGS="--full $BENCH_ARGS"  # the per-level times are in the --full line
 mkdir -p gpurun_out; export TMPDIR=/tmp
 for i in $(seq ${ROUNDS:-3}); do
   for cfg in ${CFGS:-base rc_skip=3}; do

@@ -3,6 +3,7 @@
 # librc2dgi.so and build/ab/librc2dgi_base.so (a build of another commit), ROUNDS times.
 # LIBS: other builds to cycle through instead (paths, e.g. from `_build.py exp NAME -D...`).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
+BENCH_ARGS="--full $BENCH_ARGS"  # the per-level times are in the --full line
 mkdir -p gpurun_out; export TMPDIR=/tmp
 for i in $(seq ${ROUNDS:-2}); do
   for lib in ${LIBS:-build/ab/librc2dgi_base.so radiancecascade2dglobalillumination_amd/librc2dgi.so}; do

@@ -1,6 +1,7 @@
 #!/bin/bash
 # parity of the exit proofs / tail compaction, then RC bench lines over rc_tail settings
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
+BENCH_ARGS="--full $BENCH_ARGS"  # the per-level times are in the --full line
 mkdir -p gpurun_out; export TMPDIR=/tmp
 timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py -x -q --timeout 300 --timeout-method thread -k "${TESTS:-exit_proofs or every_rc_variant or packed_fields}" > gpurun_out/t_tail.log 2>&1; rc=$?; tail -3 gpurun_out/t_tail.log; [ $rc -le 1 ] || exit $rc
 for cfg in ${CFGS:-"rc_tail=0" "rc_tail=2" "rc_tail=3" "rc_tail=4" "rc_tail=6"}; do

@@ -2,6 +2,7 @@
 # A/B of tuning knobs on one box: bench lines alternating between the knob sets in TUNES
 # ("label:--tune k=v --tune k2=v2|label2:..."), ROUNDS times; prints value, RC ms and per-level ms.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
+BENCH_ARGS="--full $BENCH_ARGS"  # the per-level times are in the --full line
 mkdir -p gpurun_out; export TMPDIR=/tmp
 IFS='|' read -r -a SETS <<< "${TUNES:-base:}"
 for i in $(seq ${ROUNDS:-2}); do

@@ -9,7 +9,7 @@ mkdir -p gpurun_out
 for v in full:radiancecascade2dglobalillumination_amd/librc2dgi.so nomerge:build/diag/librc2dgi_nomerge.so \
          nomarch:build/diag/librc2dgi_diag0.so; do
   name=${v%%:*}; lib=${v#*:}
-  RC2DGI_LIB=$PWD/$lib timeout -k 10 200 python bench.py --no-cpu-baseline --steps 20 \
+  RC2DGI_LIB=$PWD/$lib timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 20 \
     --load-tuning ${TUNING:-radiancecascade2dglobalillumination_amd/tuning/4096x4096_N6_rr2_f32.json} > gpurun_out/ablate_$name.log 2>&1 || exit $?
   python3 -c "import json,sys; d=json.loads(open('gpurun_out/ablate_$name.log').read().strip().splitlines()[-1]); print('$name', d['rc_level_ms'], d['rc_ms_per_frame'])"
 done

@@ -13,6 +13,7 @@ timeout -k 10 ${PYTEST_LIMIT:-900} python -m pytest tests -q -m gpu ${PYTEST_ARG
 rc=$?; tail -5 gpurun_out/pytest_gpu.log; echo "pytest rc=$rc"
 ok $rc || exit $rc
 echo "== bench"
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the whole line: per-level times, rooflines, input costs, CPU baseline
 timeout -k 10 ${BENCH_LIMIT:-400} python bench.py ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1
 rc=$?; tail -3 gpurun_out/bench.log; echo "bench rc=$rc"
 [ $rc -eq 0 ] || exit $rc

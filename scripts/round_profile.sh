@@ -34,6 +34,7 @@ for sc in ${PMC_SCENES:-demo random:1 dense:0}; do
   cp gpurun_out/rc_level_pmc.json profiles/rc_level_pmc.json
 done
 echo "== bench"
+SCHED="--full $SCHED"  # the final line is the whole one (per-level times, rooflines, cpu_baseline)
 timeout -k 10 400 python bench.py $SCHED > gpurun_out/bench.log 2>&1 || exit $?
 tail -1 gpurun_out/bench.log | cut -c1-200
 if [ -n "$BATCH" ]; then

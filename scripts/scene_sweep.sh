@@ -3,6 +3,7 @@
 # was not tuned on: random:0..3 (5 % occluders) and dense:0..1 (>= 25 %).  One JSON line per scene in
 # gpurun_out/scenes.jsonl.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
+BENCH_ARGS="--full $BENCH_ARGS"  # the per-level times are in the --full line
 mkdir -p gpurun_out; export TMPDIR=/tmp
 : > gpurun_out/scenes.jsonl
 for sc in ${SCENES:-demo random:0 random:1 random:2 random:3 dense:0 dense:1}; do

@@ -92,6 +92,55 @@ def test_isa_mix_classes():
     assert isa_mix.classify("ds_read_u8") == "lds" and isa_mix.classify("s_waitcnt") == "wait"
 
 
+class _FakeCtx:
+    """download() of a context whose last frame left texel i of every array at (i, i, i, i) + k."""
+
+    def __init__(self, H, W):
+        self.H, self.W = H, W
+
+    def download(self, name):
+        import numpy as np
+
+        k = {"dist": 0.0, "final_gi": 0.25, "color": 0.5}[name]
+        i = np.arange(self.H * self.W, dtype=np.float32).reshape(self.H, self.W, 1)
+        return np.repeat(i, 4, axis=2) + np.float32(k)
+
+
+def test_dump_outputs_whole_then_the_same_seeded_sample(bench, tmp_path):
+    """--dump-outputs: every output a caller receives as float32 .npy; whole arrays while they fit the
+    budget, else the same texels (ascending order, fixed seed) of each, run after run."""
+    import numpy as np
+
+    small = _FakeCtx(8, 16)
+    bench.dump_outputs(small, str(tmp_path / "a"))
+    for name in bench.DUMP_NAMES:
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, small.download(name))
+    cap = bench.DUMP_BUDGET_BYTES // len(bench.DUMP_NAMES) // 16
+    assert len(bench.DUMP_NAMES) * cap * 16 <= bench.DUMP_BUDGET_BYTES <= 64 * 10**6
+    big = _FakeCtx(1024, cap // 1024 + 1)  # one column of texels over the per-array cap
+    bench.dump_outputs(big, str(tmp_path / "b"))
+    bench.dump_outputs(big, str(tmp_path / "c"), rank=1)
+    texel = {}
+    for name in bench.DUMP_NAMES:
+        got = np.load(tmp_path / "b" / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == (cap, 4)
+        assert np.array_equal(got, np.load(tmp_path / "c" / f"{name}.rank1.npy"))
+        texel[name] = got[:, 0] - (got[0, 0] - np.floor(got[0, 0]))
+        assert np.all(np.diff(texel[name]) > 0) and texel[name][-1] < 1024 * (cap // 1024 + 1)
+        assert np.array_equal(got[:, 0], got[:, 3])
+    assert np.array_equal(texel["dist"], texel["final_gi"]) and np.array_equal(texel["dist"], texel["color"])
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= 64 * 10**6
+
+
+def test_dump_outputs_is_for_the_one_context_frame():
+    r = _run_bench(["--dump-outputs", "unused", "--batch", "2"], timeout=60)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr
+    r = _run_bench(["--help"], timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
 def _run_bench(args, env_extra=None, timeout=180):
     import subprocess
     import sys
