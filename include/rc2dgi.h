@@ -160,22 +160,36 @@ int rc2dgi_set_direction_table(rc2dgi_ctx *ctx, int level, const float *cos_sin,
 int rc2dgi_set_sky_table(rc2dgi_ctx *ctx, const float *rgb, int n);
 
 /* ---- tuning knobs (performance only; results are identical for every value).
+ * A per-level key ends in "_L<n>", n the level in decimal digits (0 .. cascade_count-1); where a key without the
+ * suffix is listed beside it, that key sets every level at once and cannot be read.  Every other key rc2dgi_set_tuning
+ * takes, rc2dgi_get_tuning returns.  A value out of range, a level out of range and an unknown key are RC2DGI_E_ARG and
+ * change nothing.  Knobs said to be 1 (or 0) "by default" without other values take any value as value != 0.
  *   "rc_variant"      RC workgroup tile shape for every level (0 .. rc_variant_count-1)
- *   "rc_variant_L<n>" the same for level n only
+ *   "rc_variant_L<n>" the same for level n only (default: 0 at levels 0..2, 13 from level 3 up)
  *   "blur_path"       blur / copy-back / merge kernels: 0 auto (fixed-tap blur with merge fused
  *                     where the sizes allow), 1 LDS-tiled blur + copy-back, then merge,
  *                     2 separate blur, copy-back and merge passes
  *   "rc_order_L<n>"   workgroup order of level n: px | py << 8 | dg << 16 = patches of px x py
- *                     probe tiles x groups of dg direction blocks (0: tile-major, the default)
- *   "poison"          debug: fill the intermediate render textures with 0xFF bytes before each
+ *                     probe tiles x groups of dg direction blocks (0: tile-major, the default of levels 0..2; from
+ *                     level 3 up the default is 2 | 2 << 8 | 8 << 16); any value >= 0
+ *   "poison"          debug, 0 (default) / 1: fill the intermediate render textures with 0xFF bytes before each
  *                     frame (rows a sharded frame never computes then read as NaN)
  *   "rc_skip"         march exit proofs from a coarse lower bound of distRT (the last sample of a
  *                     ray that misses is not read when the bound already proves the miss):
  *                     0 off, 1 auto (screens >= 2048), 2 interval only, 3 interval + screen edge
  *   "rc_wgproof"      1 (default): a workgroup whose first samples all provably miss skips the march
  *   "rc_tail" / "rc_tail_L<n>"  rays still marching after this many lockstep iterations finish one
- *                     per lane in a compacted queue (0 off; default 10)
- *   "shade_fused"     1 (default): surface records and the proofs' bound table in one pass over
+ *                     per lane in a compacted queue (-1: every ray from the start; 0 off; up to 32; default 10)
+ *   "rc_mp" / "rc_mp_L<n>"  1 (default): the one-probe tiles of a level with at least 64 direction blocks (level 3 up) skip rays that
+ *                     the directional clear table proves to miss
+ *   "rc_noproof_L<n>" 0 (default); 1: level n marches without the bound table (no exit or miss proofs)
+ *   "rc_pal"          1 (default): surface palettes -- the side pass keeps the records of a cell's hittable texels as
+ *                     a per-cell palette, and the plain-field levels march on a field that carries the palette index
+ *                     (square power-of-two screens from 4096 up to 8192)
+ *   "jfa_coset"       the first JumpFlood steps in one kernel: 2 (default) five steps (four on screens wider than
+ *                     4096), 1 four steps, 0 off
+ *   "jfa_lds"         0 (default); 1: the short JumpFlood steps stage their taps in LDS
+ *   "shade_fused"    1 (default): surface records and the proofs' bound table in one pass over
  *                     distRT where its cells are >= 64 texels (square power-of-two screens >= 4096)
  *   "shade_split"     1 (default): that pass split in two, a light scan of every cell and the records and
  *                     surface palettes of the cells holding a hittable texel

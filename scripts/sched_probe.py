@@ -21,10 +21,10 @@ sys.path.insert(0, ROOT)
 
 
 def autotune_orders():
-    """The order codes of rc2dgi_autotune's candidate list (kOrderCandidates in rc2dgi_capi.cpp)."""
+    """The order codes of rc2dgi_autotune's candidate list (kOrderCandidates in rc2dgi_autotune.cpp)."""
     import re
 
-    src = open(os.path.join(ROOT, "radiancecascade2dglobalillumination_amd", "csrc", "rc2dgi_capi.cpp")).read()
+    src = open(os.path.join(ROOT, "radiancecascade2dglobalillumination_amd", "csrc", "rc2dgi_autotune.cpp")).read()
     body = src[src.index("kOrderCandidates[][4] = {"):]
     body = body[:body.index("};")]
     quads = re.findall(r"\{(\d+), (\d+), (\d+), (\d+)\}", body)

@@ -1086,3 +1086,54 @@ def test_side_tables_match_their_restatement(RC2DGI, scene):
         assert ei.value.code == -6, name
     ctx.download_table("dclr")  # (still built: directional proofs stay on)
     ctx.close()
+
+
+def knobs_round_trip(RC2DGI, W, H, N, storage, skip=()):
+    """Set every settable key (tests/knob_cases.py) to a non-default value, read it back, put every key back to the
+    default a fresh context reports, and render: the frame must equal a fresh context's bit for bit -- no set leaves
+    a trace (a stale no-sample proof, side buffers not prepared again, a chain not freed)."""
+    from knob_cases import KNOB_CASES
+
+    color, emis = make_scene("rand:40", W, H)
+
+    def render(ctx):
+        ctx.frame(color, emis)
+        ctx.sync()
+        return {k: ctx.download(k) for k in ("color", "final_gi", "dist")}
+
+    keys = [k for k, _ in KNOB_CASES]
+
+    def readable(k):
+        """the keys that read what setting k writes (the every-level form is set-only: its levels, one by one)"""
+        per_level = k.endswith("_L<n>") or k + "_L<n>" in keys
+        return [f"{k.replace('_L<n>', '')}_L{L}" for L in range(N)] if per_level else [k]
+
+    fresh = RC2DGI(W, H, cascade_count=N, storage=storage)
+    defaults = {name: fresh.get_tuning(name) for k in keys for name in readable(k)}
+    want = render(fresh)
+    fresh.close()
+    ctx = RC2DGI(W, H, cascade_count=N, storage=storage)
+    for k, v in KNOB_CASES:
+        if (k, v) in skip:
+            continue
+        assert all(defaults[name] != v for name in readable(k)), f"{k} = {v} is a default"
+        name = k.replace("<n>", str(N - 1))
+        ctx.set_tuning(name, v)
+        for r in ([name] if k.endswith("_L<n>") else readable(k)):
+            assert ctx.get_tuning(r) == v, f"{name} = {v}: {r} reads {ctx.get_tuning(r)}"
+    for name, d in defaults.items():
+        ctx.set_tuning(name, d)
+        assert ctx.get_tuning(name) == d, name
+    got = render(ctx)
+    ctx.close()
+    for k in want:
+        assert got[k].tobytes() == want[k].tobytes(), f"{k}: {np.count_nonzero(got[k] != want[k])} values differ"
+
+
+def test_knobs_round_trip_and_leave_no_trace(RC2DGI):
+    knobs_round_trip(RC2DGI, 256, 192, 4, "f32")
+
+
+def test_knobs_round_trip_and_leave_no_trace_rgba8(RC2DGI):
+    # (tile shape 5 is an f32 kernel: RGBA8 cascades build 0, 1, 3, 6, 13 .. 19, test_every_rc_variant_is_bit_identical)
+    knobs_round_trip(RC2DGI, 64, 64, 2, "rgba8", skip={("rc_variant_L<n>", 5)})

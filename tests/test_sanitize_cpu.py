@@ -1,7 +1,8 @@
 """ASan / UBSan runs of the host code (VERDICT r1 hygiene): the CPU restatement
 (oracle/rc2dgi_oracle.c: whole frames in every mode plus row-restricted passes) and the row-strip
 planner (csrc/rc2dgi_shard.cpp: plan_frame and the JumpFlood exchange over many sizes and shard
-counts, with its invariants checked), built by tests/sanitize/Makefile with
+counts, with its invariants checked) and the tuning knob table (csrc/rc2dgi_tuning.cpp against a restatement
+of the header's contract, tests/sanitize/tuning_check.cpp), built by tests/sanitize/Makefile with
 -fsanitize=address,undefined (UB fatal).  GPU sanitizers are not available on this pool."""
 import os
 import shutil
@@ -21,7 +22,7 @@ def built():
     subprocess.run(["make", "-s", "-C", HERE], check=True)
 
 
-@pytest.mark.parametrize("exe", ["oracle_asan", "plan_asan"])
+@pytest.mark.parametrize("exe", ["oracle_asan", "plan_asan", "tuning_check"])
 def test_sanitized_run_is_clean(built, exe):
     r = subprocess.run([os.path.join(HERE, exe)], capture_output=True, text=True, env=ENV, timeout=600)
     report = r.stdout[-2000:] + r.stderr[-4000:]

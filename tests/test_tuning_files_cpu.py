@@ -55,3 +55,33 @@ def test_schedule_file_is_well_formed(path):
             assert 0 <= lc <= 31 and (base == 0 or (px > 0 and py > 0 and dg > 0 and mode in (0, 1, 2))), f"order code {code}"
     for k in d.get("knobs", {}):
         assert k in KNOBS or re.match(r"rc_(tail|mp|noproof|order|variant)_L\d+$", k), f"knob {k}"
+
+
+@pytest.fixture(scope="module")
+def table_keys():
+    """The keys of the library's knob table (csrc/rc2dgi_tuning.cpp), per-level ones as "<name>_L<n>"."""
+    import shutil
+    import subprocess
+
+    if not shutil.which("gcc") or not shutil.which("g++"):
+        pytest.skip("no host compiler")
+    here = os.path.join(ROOT, "tests", "sanitize")
+    subprocess.run(["make", "-s", "-C", here, "tuning_check"], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0")
+    r = subprocess.run([os.path.join(here, "tuning_check"), "--list"], capture_output=True, text=True, env=env,
+                       check=True, timeout=60)
+    return r.stdout.split()
+
+
+def test_every_knob_list_names_the_tables_keys(table_keys):
+    from knob_cases import KNOB_CASES
+
+    assert len(set(table_keys)) == len(table_keys) >= 25
+    assert KNOBS <= set(table_keys)
+    assert sorted(k for k, _ in KNOB_CASES) == sorted(table_keys)
+    for path in FILES:
+        for k in json.load(open(path)).get("knobs", {}):
+            assert re.sub(r"_L\d+$", "_L<n>", k) in table_keys, f"{os.path.basename(path)}: knob {k}"
+    header = open(os.path.join(ROOT, "include", "rc2dgi.h")).read()
+    for k in table_keys:
+        assert f'"{k}"' in header, f"{k} is not described in include/rc2dgi.h"
