@@ -1,6 +1,6 @@
 /* layout.c -- sizeof / offsetof of the ABI structs, as the C compiler lays them out, for
  * tests/test_host_cpu.py to compare with the C# StructLayout(Sequential) mirrors in
- * host/csharp/RC2DGINative.cs (Config, Prim). */
+ * host/csharp/RC2DGINative.cs (Config, Prim; View: tests/test_present_cpu.py). */
 #include <stddef.h>
 #include <stdio.h>
 
@@ -29,5 +29,16 @@ int main(void) {
   F(rc2dgi_prim, g);
   F(rc2dgi_prim, b);
   F(rc2dgi_prim, a);
+  printf("rc2dgi_view %zu\n", sizeof(rc2dgi_view));
+  F(rc2dgi_view, which);
+  F(rc2dgi_view, x);
+  F(rc2dgi_view, y);
+  F(rc2dgi_view, w);
+  F(rc2dgi_view, h);
+  F(rc2dgi_view, filter);
+  F(rc2dgi_view, r);
+  F(rc2dgi_view, g);
+  F(rc2dgi_view, b);
+  F(rc2dgi_view, a);
   return 0;
 }

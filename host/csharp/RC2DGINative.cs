@@ -50,7 +50,22 @@ static unsafe class RC2DGINative
     }
     [DllImport(Lib)] public static extern int rc2dgi_paint(IntPtr ctx, int which, byte* clearRgba, Prim* prims, int n);
 
+    // rc2dgi_view: one draw of the display frame (window rectangle, y down; Filter 0 = the texture's own,
+    // 1 POINT, 2 LINEAR; border A == 0: none)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct View
+    {
+        public int Which, X, Y, W, H;
+        public int Filter;
+        public byte R, G, B, A;
+    }
+    public const int MaxViews = 16;
+    [DllImport(Lib)] public static extern int rc2dgi_display_layout(ref Config cfg, View* views, int maxViews);
+    [DllImport(Lib)] public static extern int rc2dgi_compose(IntPtr ctx, View* views, int n, int outW, int outH, byte* clearRgba, void* host, int pitchBytes);
+    [DllImport(Lib)] public static extern int rc2dgi_compose_device(IntPtr ctx, View* views, int n, int outW, int outH, byte* clearRgba, void* dev, int pitchBytes);
+
     static IntPtr ctx;
+    static Config config;
     static byte[] scratch = Array.Empty<byte>();
 
     static void Check(int rc, string what)
@@ -65,6 +80,7 @@ static unsafe class RC2DGINative
         var cfg = new Config { ScreenWidth = screenWidth, ScreenHeight = screenHeight, CascadeCount = cascadeCount,
                                RenderScale = renderScale, RayRange = rayRange };
         Check(rc2dgi_create(ref cfg, out ctx), "rc2dgi_create");
+        config = cfg;
     }
 
     public static void Shutdown() { if (ctx != IntPtr.Zero) rc2dgi_destroy(ctx); ctx = IntPtr.Zero; }
@@ -94,6 +110,26 @@ static unsafe class RC2DGINative
         {
             Check(rc2dgi_download(ctx, (int)which, p, rt.Texture.Width * 4, (int)Format.RGBA8), "download");
             Raylib.UpdateTexture(rt.Texture, p);
+        }
+    }
+
+    // The display half of the main loop (RC2DGI.cs:135-165, 435-448) in one call: colorRT over the window and the
+    // seven debug thumbnails, composed on the GPU into one RGBA8 image (row 0 = top) and uploaded into
+    // windowTexture (a screen-sized RGBA8 texture from LoadTextureFromImage; draw it with DrawTexture(t, 0, 0,
+    // Color.White), unflipped).  Replaces one Download per view.
+    public static void Present(Texture2D windowTexture, bool thumbnails = true)
+    {
+        int w = windowTexture.Width, h = windowTexture.Height;
+        if (scratch.Length < w * h * 4) scratch = new byte[w * h * 4];
+        View* views = stackalloc View[8];
+        Config cfg = config;
+        cfg.ScreenWidth = w;   // (the layout follows the window: view 0 covers it, thumbnails at its right edge)
+        cfg.ScreenHeight = h;
+        int n = Math.Min(rc2dgi_display_layout(ref cfg, views, 8), 8);
+        fixed (byte* p = scratch)
+        {
+            Check(rc2dgi_compose(ctx, views, thumbnails ? n : 1, w, h, null, p, w * 4), "compose");
+            Raylib.UpdateTexture(windowTexture, p);
         }
     }
 

@@ -9,7 +9,8 @@
  *                                               frame reads is rewritten before it is read)
  *   painted colorRT/emissiveRT (RenderScene RC2DGI.cs:224-264, RedrawSceneToRTs
  *                       RC2DGI.cs:528-545)  -> rc2dgi_upload()
- *   debug thumbnails / final blit (RC2DGI.cs:135-163, 435-448) -> rc2dgi_download()
+ *   debug thumbnails / final blit (RC2DGI.cs:135-163, 435-448) -> rc2dgi_compose() (the window composed on the
+ *                                               device); rc2dgi_download() (one texture to the host, a debug path)
  *
  * Conventions:
  *   - plain C, blittable arguments (P/Invoke int/float/IntPtr), UTF-8 uniform names;
@@ -45,7 +46,9 @@ extern "C" {
 #endif
 
 #define RC2DGI_ABI_VERSION 5  /* 2: row-strip sharding entry points; 3: JumpFlood exchange planner;
-                                 4: rc2dgi_config.flags (Linux merge fallback); 5: RC2DGI_E_DEVICE */
+                                 4: rc2dgi_config.flags (Linux merge fallback); 5: RC2DGI_E_DEVICE.
+                                 rc2dgi_display_layout / rc2dgi_compose / rc2dgi_compose_device only add exports and leave
+                                 the version at 5: a host detects them by symbol lookup */
 
 typedef struct rc2dgi_ctx rc2dgi_ctx;
 
@@ -133,6 +136,64 @@ int rc2dgi_sync(rc2dgi_ctx *ctx);
 
 /* ---- outputs: any render texture, in the reference's RGBA encoding (synchronous). */
 int rc2dgi_download(rc2dgi_ctx *ctx, int which, void *host, int pitch_bytes, int format);
+
+/* ---- the display frame, composed on the device (the display half of the reference's main loop, RC2DGI.cs:135-165,
+ * 435-448: the final blit of colorRT and the seven debug thumbnails).  One kernel reads the render textures in their
+ * stored formats and writes one RGBA8 image of the window, 4 bytes a pixel, to the host (rc2dgi_compose) or into a
+ * device buffer (rc2dgi_compose_device).
+ *   Output   RGBA8, out_w x out_h, row 0 = the TOP of the window (rc2dgi_download returns GL row order, the other
+ *            way up).  pitch_bytes == 0 means out_w * 4; bytes of a row between out_w * 4 and pitch_bytes are not
+ *            written.
+ *   Clear    every pixel starts as clear_rgba; NULL = (0, 0, 0, 255), ClearBackground(Color.Black).
+ *   Draws    the views are drawn in array order, each one its texture and then its border.  Every draw blends into
+ *            the 8-bit framebuffer with the blend of the RGBA8 passes, in every storage mode (the window is RGBA8
+ *            whatever the render textures are): a8 = q8(src.a) and per channel, alpha included,
+ *            min(255, mul8(q8(src_c), a8) + mul8(dst_c, 255 - a8)), q8(x) = rint(clamp(x, 0, 1) * 255),
+ *            mul8(x, y) = (x * y * 257 + 32768) >> 16.
+ *   Sampling for a window pixel (px, py) inside the view, i = px - x and j = h - 1 - (py - y) (the flip is the
+ *            reference's negative source height); u = ((float)i + 0.5f) / (float)w, v = ((float)j + 0.5f) / (float)h.
+ *            POINT takes the texel NEAREST + REPEAT names; LINEAR the four REPEAT-wrapped taps and weights of GL's
+ *            LINEAR filter, lerped as the texture's storage does: fma lerps on floats (f32; f16 after the exact
+ *            unpack), 8.8 fixed point on the bytes (rgba8).
+ *   Texels   a texel's value is what rc2dgi_download returns for that texture as floats: JUMP1 / JUMP2 decoded to
+ *            (u, v, 0, 1) or no seed (0, 0, 0, 1), DIST to its hi / lo bytes, COLOR the input before the first frame
+ *            and the merged output after, GI2 (0, 0, 0, 1) with one cascade, FINAL_GI the alias of GI1 / GI2.
+ *   Border   the pixels of the rectangle with px == x, px == x + w - 1, py == y or py == y + h - 1, blended with the
+ *            border colour's bytes as the 8-bit source (a == 0: no border).
+ * Limits: a 1:1 view is exactly the reference's blit.  For scaled views the texcoord form above is this library's
+ * statement (not probed against a GL implementation); the border is a one-pixel frame, not raylib's GL line
+ * rasterisation; text and the GUI are the caller's.
+ * Errors: RC2DGI_E_ARG for a null context, view list or destination, n outside 1 .. RC2DGI_MAX_VIEWS, w or h below 1,
+ * out_w or out_h outside 1 .. 32768, a pitch smaller than a row or not a multiple of 4, a device destination not
+ * aligned to 4 bytes, a bad `which` or `filter`; RC2DGI_E_UNSUPPORTED for RC2DGI_FILTER_LINEAR on a texture other
+ * than GI1 / GI2 / BLUR / FINAL_GI and for any call on a row-strip shard (world > 1: its textures hold windows and
+ * bands). */
+enum { RC2DGI_FILTER_RT = 0,     /* the filter the reference sets on that texture (RC2DGI.cs:89-98):
+                                    LINEAR for GI1 / GI2 / BLUR / FINAL_GI, POINT for the rest */
+       RC2DGI_FILTER_POINT = 1, RC2DGI_FILTER_LINEAR = 2 };
+#define RC2DGI_MAX_VIEWS 16
+
+typedef struct rc2dgi_view {
+  int which;                 /* rc2dgi_rt, RC2DGI_RT_FINAL_GI allowed */
+  int x, y, w, h;            /* destination rectangle in window pixels, y down; w, h >= 1; may hang over the
+                                window on any side (clipped) */
+  int filter;                /* RC2DGI_FILTER_* */
+  unsigned char r, g, b, a;  /* border colour; a == 0: no border */
+} rc2dgi_view;               /* 28 bytes, blittable */
+
+/* host-only, no device: the reference's display (RC2DGI.cs:139-163) for this config -- view 0 is COLOR at
+ * (0, 0, W, H) without a border, then the thumbnails COLOR, EMISSIVE, JUMP2, DIST, GI1, GI2, TEMP, thumbnail k at
+ * (W - 110, 10 * (k + 1) + 100 * k, 100, 100) with RC2DGI_FILTER_RT and raylib's Red (230, 41, 55, 255) as border.
+ * Writes up to max_views views; returns 8. */
+int rc2dgi_display_layout(const rc2dgi_config *cfg, rc2dgi_view *views, int max_views);
+/* synchronous w.r.t. `host`: synchronises the context stream (a cascade chain timeout returns RC2DGI_E_DEVICE, as
+ * rc2dgi_download does), composes into a context-owned device buffer and copies out_h rows of out_w * 4 bytes */
+int rc2dgi_compose(rc2dgi_ctx *ctx, const rc2dgi_view *views, int n, int out_w, int out_h,
+                   const unsigned char *clear_rgba, void *host, int pitch_bytes);
+/* enqueues the kernel on the context stream, after whatever frame is in flight, and returns; `dev` is a device
+ * pointer on the context's device that the caller keeps alive until rc2dgi_sync() */
+int rc2dgi_compose_device(rc2dgi_ctx *ctx, const rc2dgi_view *views, int n, int out_w, int out_h,
+                          const unsigned char *clear_rgba, void *dev, int pitch_bytes);
 
 /* cascade resolution (RC2DGI.cs:70-77), JFA step count (RC2DGI.cs:289-292) and which
  * giRT holds the final GI (1 or 2, RC2DGI.cs:365) */

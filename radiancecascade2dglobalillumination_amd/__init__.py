@@ -6,6 +6,6 @@ a C ABI (include/rc2dgi.h, librc2dgi.so).
   operator interface (rc2dgi.py);
 * :mod:`scenes` -- synthetic painted-scene inputs for tests and benchmarks.
 """
-from .rc2dgi import RC2DGI, RC2DGIError, abi_version, load_library  # noqa: F401
+from .rc2dgi import RC2DGI, RC2DGIError, View, abi_version, display_layout, load_library  # noqa: F401
 
-__all__ = ["RC2DGI", "RC2DGIError", "abi_version", "load_library"]
+__all__ = ["RC2DGI", "RC2DGIError", "View", "abi_version", "display_layout", "load_library"]

@@ -1,0 +1,149 @@
+// rc2dgi_compose.cpp -- the display frame of the C ABI (include/rc2dgi.h): the reference's display layout
+// (RC2DGI.cs:139-163), and the views resolved to their stored textures for k_present (rc2dgi_present.hip).
+#include "rc2dgi_ctx.h"
+
+namespace {
+
+constexpr int kMaxOut = 32768;
+
+bool linear_rt(int which) {  // the textures the reference filters LINEAR (RC2DGI.cs:89-98)
+  return which == RC2DGI_RT_GI1 || which == RC2DGI_RT_GI2 || which == RC2DGI_RT_BLUR || which == RC2DGI_RT_FINAL_GI;
+}
+
+unsigned pack_rgba(const unsigned char *p) {
+  return (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16) | ((unsigned)p[3] << 24);
+}
+
+int clampi(long long v, int lo, int hi) { return (int)std::min<long long>(std::max<long long>(v, lo), hi); }
+
+// Validate the call and resolve every view to source pointer, pitch, axes, storage kind and filter, as
+// rc2dgi_download reads that texture.  Views that miss the window are dropped.
+int resolve_views(rc2dgi_ctx *c, const rc2dgi_view *views, int n, int out_w, int out_h, const unsigned char *clear,
+                  const void *dst, int *pitch_bytes, PresentArgs &a) {
+  if (!c || !views || !dst) return fail(c, RC2DGI_E_ARG, "null argument");
+  RC2DGI_USABLE(c);
+  if (c->world > 1)
+    return fail(c, RC2DGI_E_UNSUPPORTED, "a row-strip shard's textures hold windows and bands: compose on an unsharded context");
+  if (n < 1 || n > RC2DGI_MAX_VIEWS) return fail(c, RC2DGI_E_ARG, "1 .. RC2DGI_MAX_VIEWS views");
+  if (out_w < 1 || out_h < 1 || out_w > kMaxOut || out_h > kMaxOut)
+    return fail(c, RC2DGI_E_ARG, "the window is 1 .. 32768 pixels on each side");
+  if (*pitch_bytes == 0) *pitch_bytes = out_w * 4;
+  if (*pitch_bytes < out_w * 4) return fail(c, RC2DGI_E_ARG, "pitch smaller than a row");
+  if (*pitch_bytes % 4 != 0) return fail(c, RC2DGI_E_ARG, "the pitch is a multiple of 4 bytes");
+  static const unsigned char black[4] = {0, 0, 0, 255};
+  a.n = 0;
+  a.clear = pack_rgba(clear ? clear : black);
+  a.out_w = out_w;
+  a.out_h = out_h;
+  const bool u8 = rgba8(c);
+  for (int k = 0; k < n; ++k) {
+    const rc2dgi_view &q = views[k];
+    const std::string tag = "view " + std::to_string(k) + ": ";
+    if (q.which < RC2DGI_RT_COLOR || q.which > RC2DGI_RT_FINAL_GI) return fail(c, RC2DGI_E_ARG, tag + "bad render texture id");
+    if (q.w < 1 || q.h < 1) return fail(c, RC2DGI_E_ARG, tag + "w and h are at least 1");
+    if (q.filter != RC2DGI_FILTER_RT && q.filter != RC2DGI_FILTER_POINT && q.filter != RC2DGI_FILTER_LINEAR)
+      return fail(c, RC2DGI_E_ARG, tag + "bad filter");
+    if (q.filter == RC2DGI_FILTER_LINEAR && !linear_rt(q.which))
+      return fail(c, RC2DGI_E_UNSUPPORTED, tag + "LINEAR is for GI1 / GI2 / BLUR / FINAL_GI");
+    PresentView v{};
+    v.linear = q.filter == RC2DGI_FILTER_LINEAR || (q.filter == RC2DGI_FILTER_RT && linear_rt(q.which));
+    int which = q.which;
+    if (which == RC2DGI_RT_FINAL_GI) which = (c->N % 2 == 0) ? RC2DGI_RT_GI2 : RC2DGI_RT_GI1;
+    const bool scr = !linear_rt(which);
+    v.nx = scr ? c->W : c->CW;
+    v.ny = scr ? c->H : c->CH;
+    v.powx = is_pow2(v.nx);
+    v.powy = is_pow2(v.ny);
+    v.pitch = scr ? c->sd.pitch : c->cd.pitch;
+    const int gi_kind = u8 ? PK_U8 : (c->storage == RC2DGI_STORAGE_F16 ? PK_F16 : PK_F32);
+    switch (which) {
+      case RC2DGI_RT_COLOR: v.src = c->frame_done ? c->color_out : c->color_in; v.kind = PK_F32; break;
+      case RC2DGI_RT_EMISSIVE: v.src = c->emissive; v.kind = PK_F32; break;
+      case RC2DGI_RT_TEMP: v.src = c->temp; v.kind = PK_F32; break;
+      case RC2DGI_RT_JUMP1: v.src = c->jump1; v.kind = u8 ? PK_JUMP8 : PK_JUMP; break;
+      case RC2DGI_RT_JUMP2: v.src = c->jump2; v.kind = u8 ? PK_JUMP8 : PK_JUMP; break;
+      case RC2DGI_RT_DIST: v.src = c->dist; v.kind = u8 ? PK_DIST8 : PK_DIST; break;
+      case RC2DGI_RT_GI1: v.src = c->gi1; v.kind = gi_kind; break;
+      case RC2DGI_RT_GI2: v.src = c->gi2; v.kind = c->N == 1 ? PK_CONST : gi_kind; break;  // never drawn with one cascade
+      default: v.src = c->blur; v.kind = u8 ? PK_U8 : PK_F32; break;  // RC2DGI_RT_BLUR
+    }
+    v.x = q.x;
+    v.y = q.y;
+    v.w = q.w;
+    v.h = q.h;
+    v.border = q.a ? pack_rgba(&q.r) : 0u;
+    const long long x1 = (long long)q.x + q.w, y1 = (long long)q.y + q.h;
+    v.cx0 = clampi(q.x, 0, out_w);
+    v.cx1 = clampi(x1, 0, out_w);
+    v.cy0 = clampi(q.y, 0, out_h);
+    v.cy1 = clampi(y1, 0, out_h);
+    if (v.cx0 >= v.cx1 || v.cy0 >= v.cy1) continue;  // wholly outside the window
+    const bool blit = !v.linear && q.w == v.nx && q.h == v.ny && (v.kind == PK_F32 || v.kind == PK_U8);
+    const int b = q.a ? 1 : 0;
+    if (blit) {
+      v.fx0 = clampi((long long)q.x + b, 0, out_w);
+      v.fx1 = clampi(x1 - b, 0, out_w);
+      v.fy0 = clampi((long long)q.y + b, 0, out_h);
+      v.fy1 = clampi(y1 - b, 0, out_h);
+    }
+    a.v[a.n++] = v;
+  }
+  return RC2DGI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rc2dgi_display_layout(const rc2dgi_config *cfg, rc2dgi_view *views, int max_views) {
+  if (!cfg || max_views < 0 || (max_views > 0 && !views)) return RC2DGI_E_ARG;
+  const int W = cfg->screen_width, H = cfg->screen_height;
+  // DrawTexturePro(colorRT.Texture, ..) over the window, then DrawDebugRT per thumbnail (RC2DGI.cs:139-163, 435-448)
+  static const int thumbs[7] = {RC2DGI_RT_COLOR, RC2DGI_RT_EMISSIVE, RC2DGI_RT_JUMP2, RC2DGI_RT_DIST,
+                                RC2DGI_RT_GI1,   RC2DGI_RT_GI2,      RC2DGI_RT_TEMP};
+  for (int k = 0; k < 8 && k < max_views; ++k) {
+    rc2dgi_view v{};
+    if (k == 0) {
+      v = rc2dgi_view{RC2DGI_RT_COLOR, 0, 0, W, H, RC2DGI_FILTER_RT, 0, 0, 0, 0};
+    } else {
+      const int t = k - 1;
+      v = rc2dgi_view{thumbs[t], W - 110, 10 * (t + 1) + 100 * t, 100, 100, RC2DGI_FILTER_RT, 230, 41, 55, 255};
+    }
+    views[k] = v;
+  }
+  return 8;
+}
+
+int rc2dgi_compose_device(rc2dgi_ctx *c, const rc2dgi_view *views, int n, int out_w, int out_h,
+                          const unsigned char *clear_rgba, void *dev, int pitch_bytes) {
+  PresentArgs a;
+  if (int rc = resolve_views(c, views, n, out_w, out_h, clear_rgba, dev, &pitch_bytes, a)) return rc;
+  if (reinterpret_cast<uintptr_t>(dev) % 4 != 0) return fail(c, RC2DGI_E_ARG, "the destination is aligned to 4 bytes");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, launch_present(a, dev, pitch_bytes, c->stream));
+  return RC2DGI_OK;
+}
+
+int rc2dgi_compose(rc2dgi_ctx *c, const rc2dgi_view *views, int n, int out_w, int out_h, const unsigned char *clear_rgba,
+                   void *host, int pitch_bytes) {
+  PresentArgs a;
+  if (int rc = resolve_views(c, views, n, out_w, out_h, clear_rgba, host, &pitch_bytes, a)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = check_chain(c)) return rc;
+  const size_t dpitch = (size_t)round_up(out_w, 4) * 4, need = dpitch * (size_t)out_h;  // 16-byte rows: vector stores
+  if (need > c->present_cap) {  // (the stream is idle: nothing reads the old image)
+    if (c->present_buf) HIPCHK(c, hipFree(c->present_buf));
+    c->present_buf = nullptr;
+    c->present_cap = 0;
+    HIPCHK(c, alloc(&c->present_buf, need));
+    c->present_cap = need;
+  }
+  HIPCHK(c, launch_present(a, c->present_buf, (int)dpitch, c->stream));
+  HIPCHK(c, hipMemcpy2DAsync(host, (size_t)pitch_bytes, c->present_buf, dpitch, (size_t)out_w * 4, (size_t)out_h,
+                             hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RC2DGI_OK;
+}
+
+}  // extern "C"

@@ -48,6 +48,32 @@ class Prim(ctypes.Structure):
                 ("a", ctypes.c_ubyte)]
 
 
+FILTER_RT, FILTER_POINT, FILTER_LINEAR = 0, 1, 2
+MAX_VIEWS = 16
+RED = (230, 41, 55, 255)  # raylib Color.Red, the thumbnails' border (RC2DGI.cs:435-448)
+
+
+class View(ctypes.Structure):
+    """rc2dgi_view: one draw of the display frame -- render texture `which` into the window rectangle
+    (x, y, w, h) (y down, clipped to the window), then a one-pixel border (a == 0: none)."""
+    _fields_ = [("which", ctypes.c_int), ("x", ctypes.c_int), ("y", ctypes.c_int), ("w", ctypes.c_int),
+                ("h", ctypes.c_int), ("filter", ctypes.c_int), ("r", ctypes.c_ubyte), ("g", ctypes.c_ubyte),
+                ("b", ctypes.c_ubyte), ("a", ctypes.c_ubyte)]
+
+    @classmethod
+    def make(cls, which, x, y, w, h, filter=FILTER_RT, border=(0, 0, 0, 0)):
+        """which: a name of RT or an rc2dgi_rt id."""
+        return cls(RT[which] if isinstance(which, str) else int(which), int(x), int(y), int(w), int(h), int(filter),
+                   *(int(v) for v in border))
+
+
+def _view_array(views):
+    arr = (View * max(len(views), 1))()
+    for k, v in enumerate(views):
+        arr[k] = v if isinstance(v, View) else View.make(*v)
+    return arr
+
+
 class _Config(ctypes.Structure):
     _fields_ = [("screen_width", ctypes.c_int), ("screen_height", ctypes.c_int), ("cascade_count", ctypes.c_int),
                 ("render_scale", ctypes.c_float), ("ray_range", ctypes.c_float), ("storage", ctypes.c_int),
@@ -115,6 +141,11 @@ def load_library(path: Optional[str] = None):
         "rc2dgi_download_table": ([vp, ctypes.c_int, vp, ctypes.c_int], ctypes.c_int),
         "rc2dgi_plan_group_waits": ([ctypes.POINTER(_Config), ctypes.c_int, ctypes.c_int, ctypes.c_int, ip,
                                      ctypes.c_int], ctypes.c_int),
+        "rc2dgi_display_layout": ([ctypes.POINTER(_Config), ctypes.POINTER(View), ctypes.c_int], ctypes.c_int),
+        "rc2dgi_compose": ([vp, ctypes.POINTER(View), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                            ctypes.POINTER(ctypes.c_ubyte), vp, ctypes.c_int], ctypes.c_int),
+        "rc2dgi_compose_device": ([vp, ctypes.POINTER(View), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                   ctypes.POINTER(ctypes.c_ubyte), vp, ctypes.c_int], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -301,6 +332,49 @@ class RC2DGI:
                                             shape[1] * (4 if fmt == FMT_RGBA8 else 16), fmt), f"download {which}")
         return out
 
+    # ---------------------------------------------------------------- the display frame, composed on the GPU
+    def _compose_args(self, views, size, clear):
+        w, h = (self.screen_width, self.screen_height) if size is None else (int(size[0]), int(size[1]))
+        cl = None if clear is None else (ctypes.c_ubyte * 4)(*[int(v) for v in clear])
+        return _view_array(views), len(views), w, h, cl
+
+    def compose(self, views, size=None, clear=None) -> np.ndarray:
+        """The window (RC2DGI.cs:135-165) as one RGBA8 image uint8[h, w, 4], row 0 = top: `clear` (default
+        opaque black), then the views in order (View, or tuples for View.make), blended in 8 bits
+        (rc2dgi_compose).  size: (w, h), default the screen.  Synchronous."""
+        arr, n, w, h, cl = self._compose_args(views, size, clear)
+        out = np.empty((max(h, 0), max(w, 0), 4), np.uint8)
+        self._check(self._L.rc2dgi_compose(self._h, arr, n, w, h, cl, out.ctypes.data_as(ctypes.c_void_p), w * 4),
+                    "compose")
+        return out
+
+    def compose_into(self, dst, views, size=None, clear=None, pitch=None) -> None:
+        """The same image into device memory, enqueued on the context stream (rc2dgi_compose_device; sync()
+        or order the stream before reading).  dst: a torch uint8 tensor [h, w, 4] on this context's GPU --
+        its rows may be padded, the pitch is the tensor's row stride -- or a device pointer (int) with
+        size = (w, h) and pitch in bytes (default w * 4).  Bytes of a row past w * 4 are not written."""
+        if hasattr(dst, "data_ptr"):
+            t = dst
+            if not getattr(t, "is_cuda", False) or str(t.dtype) != "torch.uint8":
+                raise TypeError("compose_into: expected a uint8 tensor on the GPU")
+            if t.dim() != 3 or t.shape[2] != 4 or t.stride(2) != 1 or t.stride(1) != 4:
+                raise ValueError("compose_into: expected shape [h, w, 4] with contiguous pixels")
+            if size is None:
+                size = (int(t.shape[1]), int(t.shape[0]))
+            elif (int(size[0]), int(size[1])) != (int(t.shape[1]), int(t.shape[0])):
+                raise ValueError(f"compose_into: size {tuple(size)} does not match the tensor {tuple(t.shape)}")
+            ptr, pitch = t.data_ptr(), int(t.stride(0))
+        else:
+            ptr = int(dst)
+        arr, n, w, h, cl = self._compose_args(views, size, clear)
+        self._check(self._L.rc2dgi_compose_device(self._h, arr, n, w, h, cl, ctypes.c_void_p(ptr),
+                                                  int(pitch) if pitch else 0), "compose_into")
+
+    def display_frame(self, thumbnails: bool = True) -> np.ndarray:
+        """The reference's display: colorRT over the window and, with `thumbnails`, its seven debug views."""
+        views = display_layout(self.screen_width, self.screen_height)
+        return self.compose(views if thumbnails else views[:1])
+
     def set_tuning(self, key: str, value: int) -> None:
         """Performance knobs (results are identical for every value), e.g. rc_variant."""
         self._check(self._L.rc2dgi_set_tuning(self._h, key.encode(), int(value)), f"set_tuning {key}")
@@ -442,6 +516,19 @@ def do_group(ctxs: Sequence["RC2DGI"]) -> None:
         raise RC2DGIError(rc, "rc2dgi_do_group: " + "; ".join(m.decode() for m in msgs if m))
 
 
+def display_layout(W: int, H: int, max_views: int = 8):
+    """Host-only: the reference's display for a W x H window (rc2dgi_display_layout) as a list of View --
+    colorRT over the window, then the thumbnails color, emissive, jump2, dist, gi1, gi2, temp.  The layout
+    depends on the window size alone."""
+    L = load_library()
+    cfg = _Config(screen_width=W, screen_height=H)  # (the only fields rc2dgi_display_layout reads)
+    arr = (View * max(max_views, 1))()
+    n = L.rc2dgi_display_layout(ctypes.byref(cfg), arr, max_views)
+    if n < 0:
+        raise RC2DGIError(n, "rc2dgi_display_layout")
+    return [View.from_buffer_copy(arr[k]) for k in range(min(n, max_views))]
+
+
 def plan_rows(W: int, H: int, N: int, blur_radius: float, rank: int, world: int, pass_id: int,
               render_scale: float = 1.0):
     """Host-only planner: [(begin, end), ...] rows shard `rank` of `world` computes for a pass
@@ -502,4 +589,5 @@ def plan_jfa_window(W: int, H: int, N: int, rank: int, world: int, step: int, re
 
 
 __all__ = ["RC2DGI", "RC2DGIError", "load_library", "abi_version", "RT", "PASS_NAMES", "shard_unique_id", "do_group",
-           "plan_rows", "plan_jfa_exchange", "plan_jfa_window", "PLAN_JFA", "PLAN_LEVEL", "PLAN_BLUR", "PLAN_MERGE"]
+           "plan_rows", "plan_jfa_exchange", "plan_jfa_window", "PLAN_JFA", "PLAN_LEVEL", "PLAN_BLUR", "PLAN_MERGE",
+           "View", "display_layout", "FILTER_RT", "FILTER_POINT", "FILTER_LINEAR", "MAX_VIEWS"]
