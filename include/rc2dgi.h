@@ -61,7 +61,8 @@ typedef enum rc2dgi_status {
   RC2DGI_E_UNSUPPORTED = -5,  /* valid request this build does not implement */
   RC2DGI_E_STATE = -6,        /* call not valid in the current state */
   RC2DGI_E_DEVICE = -7        /* a device-side check failed: an enqueued frame's results are wrong (the cascade
-                                 chain's wait timed out; reported by the next rc2dgi_sync / _download / _do) */
+                                 chain's wait timed out; reported by the next rc2dgi_sync / _download /
+                                 _download_level / _compose / _do / _do_phase) */
 } rc2dgi_status;
 
 typedef enum rc2dgi_storage {
@@ -126,7 +127,11 @@ int rc2dgi_get_uniform(rc2dgi_ctx *ctx, const char *name, float *v, int n);
 
 /* ---- inputs: the painted colorRT / emissiveRT (W x H).  Host source: synchronous copy.
  * Device source (a HIP device pointer on the context's device): enqueued on the context
- * stream, the caller keeps the source alive until rc2dgi_sync(). */
+ * stream, the caller keeps the source alive until rc2dgi_sync().
+ * pitch_bytes == 0 means a tight row (W * 4 or W * 16 bytes); bytes of a row past that are not read.
+ * Errors: RC2DGI_E_ARG for a null context or source, a `which` other than COLOR / EMISSIVE, a bad format, a pitch
+ * smaller than a row and, for rc2dgi_upload_device with RC2DGI_FMT_RGBA8, a device source not aligned to 4 bytes or a
+ * pitch not a multiple of 4 (the kernel loads a pixel as one dword). */
 int rc2dgi_upload(rc2dgi_ctx *ctx, int which, const void *host, int pitch_bytes, int format);
 int rc2dgi_upload_device(rc2dgi_ctx *ctx, int which, const void *dev, int pitch_bytes, int format);
 
@@ -134,7 +139,9 @@ int rc2dgi_upload_device(rc2dgi_ctx *ctx, int which, const void *dev, int pitch_
 int rc2dgi_do(rc2dgi_ctx *ctx);
 int rc2dgi_sync(rc2dgi_ctx *ctx);
 
-/* ---- outputs: any render texture, in the reference's RGBA encoding (synchronous). */
+/* ---- outputs: any render texture, in the reference's RGBA encoding (synchronous).  RC2DGI_FMT_RGBA8 converts as
+ * q8 does: rint(clamp(x, 0, 1) * 255), NaN -> 0.  pitch_bytes == 0 means a tight row; bytes of a row past the
+ * texture's own are not written. */
 int rc2dgi_download(rc2dgi_ctx *ctx, int which, void *host, int pitch_bytes, int format);
 
 /* ---- the display frame, composed on the device (the display half of the reference's main loop, RC2DGI.cs:135-165,
@@ -262,8 +269,9 @@ int rc2dgi_set_sky_table(rc2dgi_ctx *ctx, const float *rgb, int n);
  *   "rc_chain"        0 (default); 1 / 2: the levels below the top in ONE launch of 16x16x1 tiles, a tile
  *                     starting when the upper tiles under its footprint are written (2: unrolled march);
  *                     4: the top level in that launch too; f32 cascades, one process.  A wait that times out
- *                     makes the next rc2dgi_sync / rc2dgi_download / rc2dgi_do return RC2DGI_E_DEVICE and turns
- *                     the chain off for the context (never a silent wrong frame)
+ *                     makes the next rc2dgi_sync / rc2dgi_download / rc2dgi_download_level / rc2dgi_compose /
+ *                     rc2dgi_do / rc2dgi_do_phase return RC2DGI_E_DEVICE and turns the chain off for the context
+ *                     (never a silent wrong frame)
  *   "rc_chain_spin"   diagnostic: polls per chain wait (0: the default bound; -1: every wait times out at once)
  *   "jfa_rows"        0 (default), 4, 8: the short isotropic JumpFlood steps (offsets 1, 2, 4 on square power-of-two
  *                     screens) with that many consecutive rows per lane, each tap row loaded once (measured no faster)

@@ -62,7 +62,8 @@ bool chain_active(const rc2dgi_ctx *c) {
 
 // A chained frame whose workgroup stopped waiting for its upper tiles merged texels that were not written: no
 // silent wrong frame.  The kernel sets a host-mapped word; the next rc2dgi_sync / rc2dgi_download /
-// rc2dgi_do returns RC2DGI_E_DEVICE and the context falls back to one launch per level from then on.
+// rc2dgi_download_level / rc2dgi_compose / rc2dgi_do / rc2dgi_do_phase returns RC2DGI_E_DEVICE and the context
+// falls back to one launch per level from then on.
 int check_chain(rc2dgi_ctx *c) {
   if (!c->chain || !rc_chain_take_error(c->chain)) return RC2DGI_OK;
   c->rc_chain = 0;

@@ -9,8 +9,8 @@ bool screen_rt(int which) {
          which == RC2DGI_RT_JUMP2 || which == RC2DGI_RT_DIST || which == RC2DGI_RT_TEMP;
 }
 
-inline unsigned char to_unorm8(float x) {  // GL readback conversion: clamp, round to nearest even
-  float v = x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x);
+inline unsigned char to_unorm8(float x) {  // GL readback conversion: clamp, round to nearest even; NaN -> 0 as q8 does
+  float v = x > 0.0f ? (x > 1.0f ? 1.0f : x) : 0.0f;  // (a NaN compares false: the rows a strip shard does not hold)
   return (unsigned char)std::nearbyint(v * 255.0f);
 }
 
@@ -242,6 +242,10 @@ int rc2dgi_upload_device(rc2dgi_ctx *c, int which, const void *dev, int pitch_by
   if (row < 0) return fail(c, RC2DGI_E_ARG, "bad format");
   if (pitch_bytes == 0) pitch_bytes = row;
   if (pitch_bytes < row) return fail(c, RC2DGI_E_ARG, "pitch smaller than a row");
+  if (format == RC2DGI_FMT_RGBA8) {  // (k_unorm8_to_f32 loads a pixel as one dword)
+    if (pitch_bytes % 4 != 0) return fail(c, RC2DGI_E_ARG, "the pitch is a multiple of 4 bytes");
+    if (reinterpret_cast<uintptr_t>(dev) % 4 != 0) return fail(c, RC2DGI_E_ARG, "the source is aligned to 4 bytes");
+  }
   HIPCHK(c, hipSetDevice(c->device));
   float4 *dst = which == RC2DGI_RT_COLOR ? c->color_in : c->emissive;
   if (format == RC2DGI_FMT_RGBA32F) {
@@ -460,12 +464,14 @@ int rc2dgi_download_level(rc2dgi_ctx *c, int level, void *host, int pitch_bytes,
   RC2DGI_USABLE(c);
   if (!c->keep_levels || !c->have_frame) return fail(c, RC2DGI_E_STATE, "enable keep_levels and run a frame first");
   if (level < 0 || level >= c->N) return fail(c, RC2DGI_E_ARG, "level out of range");
+  if (format != RC2DGI_FMT_RGBA32F && format != RC2DGI_FMT_RGBA8) return fail(c, RC2DGI_E_ARG, "bad format");
   if (format != RC2DGI_FMT_RGBA32F) return fail(c, RC2DGI_E_UNSUPPORTED, "levels download as RGBA32F");
   const int row = c->CW * 16;
   if (pitch_bytes == 0) pitch_bytes = row;
   if (pitch_bytes < row) return fail(c, RC2DGI_E_ARG, "pitch smaller than a row");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = check_chain(c)) return rc;
   if (gi_bytes(c) != 16) {
     std::vector<float4> img((size_t)c->CW * c->CH);
     int rc = fetch_gi(c, c->level_bufs[level], img, gi_bytes(c));

@@ -504,6 +504,7 @@ int rc2dgi_do(rc2dgi_ctx *c) {
 int rc2dgi_do_phase(rc2dgi_ctx *c, int phase) {
   if (!c) return RC2DGI_E_ARG;
   RC2DGI_USABLE(c);
+  if (int rc = check_chain(c)) return rc;  // (an earlier chained frame that has completed)
   if (phase != 1 && phase != 2) return fail(c, RC2DGI_E_ARG, "phase is 1 or 2");
   if (phase == 1 && c->strip)
     return fail(c, RC2DGI_E_STATE,

@@ -210,6 +210,10 @@ hipError_t launch_rc_top(const RcLevelArgs &a, RcParams P, hipStream_t st) {
   P.lgw = 0;
   while ((1 << P.lgw) < P.s.pitch) ++P.lgw;
   if (P.cpal && (1 << P.lgw) != P.s.pitch) P.cpal = nullptr;
+  // (row-strip shards with strip tables hold no record texture: a.shade is null there and RecSrc derives the record
+  // of a hit without a palette entry from the inputs, as rc_tile_params sets it up for every other variant)
+  P.rcol = a.rec_color;
+  P.remi = a.rec_emis;
 #define RC2DGI_TOP(G)                                                                                         \
   hipLaunchKernelGGL(k_rc_top<G>, dim3(nwg), dim3(256), 0, st, P, reinterpret_cast<typename G::T *>(a.out),   \
                      a.dist, a.shade, a.dirs, a.sky)

@@ -664,14 +664,16 @@ def test_rc_reciprocal_divisions_are_bit_identical(RC2DGI, W, H, N, rr, rs, chai
 
 
 @pytest.mark.parametrize("W,H,N,rs", [(1200, 900, 6, 1.0), (200, 120, 3, 1.0), (320, 256, 4, 0.5), (96, 4000, 4, 1.0),
-                                      (4000, 96, 4, 1.0), (6000, 2000, 4, 1.0)])
+                                      (4000, 96, 4, 1.0), (6000, 2000, 4, 1.0), (8188, 8, 3, 1.0), (8, 8188, 3, 1.0)])
 @pytest.mark.parametrize("scene", ["demo", "rand:63"])
 def test_jfa_texcoord_table_is_bit_identical(RC2DGI, W, H, N, rs, scene):
     """The float-path JumpFlood steps (non-power-of-two screens) take every fragTexCoord from the context's table of
     (i + 0.5) / n (tuning jfa_tab 1) or from x * (1/n) with one fused correction, proven equal to the division for
     every index on the host (jfa_tab 2, the default) instead of dividing per tap: jumpRT1 / jumpRT2, the distance
-    field and the frame are unchanged, poisoned intermediates; W + H above the table's limit (6000 + 2000) divides
-    under jfa_tab 1."""
+    field and the frame are unchanged, poisoned intermediates.  6000 x 2000 is the largest case inside the table
+    (W + H <= 8192); the thin 8188 x 8 and 8 x 8188 screens (W + H = 8196) are over its limit, where jfa_tab 1 divides
+    per tap -- those two are also compared with the oracle, so the fallback is checked against something other than
+    itself."""
     color, emis = make_scene(scene, W, H)
     ctx = RC2DGI(W, H, cascade_count=N, ray_range=2.0, render_scale=rs)
     ctx.upload("color", color)
@@ -689,6 +691,12 @@ def test_jfa_texcoord_table_is_bit_identical(RC2DGI, W, H, N, rs, scene):
             assert np.array_equal(out[0][k].view(np.uint8), out[tab][k].view(np.uint8)), \
                 f"jfa_tab {tab} {k}: {np.count_nonzero(out[0][k] != out[tab][k])}"
     ctx.close()
+    if W + H > 8192:
+        ref = oracle_dict(oracle.frame(oracle.Params(W=W, H=H, N=N, ray_range=2.0, render_scale=rs), color, emis))
+        for tab in (0, 1, 2):
+            for k in out[tab]:
+                assert np.array_equal(out[tab][k].view(np.uint8), ref[k].view(np.uint8)), \
+                    f"jfa_tab {tab} {k} vs the oracle: {np.count_nonzero(out[tab][k] != ref[k])}"
 
 
 @pytest.mark.parametrize("W,H,N,storage", [(64, 64, 3, "f32"), (128, 128, 3, "f32"), (256, 256, 4, "f32"),
@@ -804,17 +812,20 @@ def test_cascade_chain_is_bit_identical(RC2DGI, W, H, N, rr, scene):
     ctx.close()
 
 
-@pytest.mark.parametrize("report", ["sync", "download", "do"])
+@pytest.mark.parametrize("report", ["sync", "download", "do", "download_level", "do_phase"])
 def test_cascade_chain_timeout_is_an_error(RC2DGI, report):
     """A chain workgroup that stops waiting merges upper tiles that were not written, so the frame is wrong: the
-    next rc2dgi_sync / rc2dgi_download / rc2dgi_do returns RC2DGI_E_DEVICE (-7), names the chain, and the context
-    falls back to one launch per level -- the following frame is bit-identical to the unchained one.  The
-    diagnostic knob rc_chain_spin -1 makes every wait time out at once (the product bound is 2^20 polls)."""
+    next rc2dgi_sync / rc2dgi_download / rc2dgi_download_level / rc2dgi_do / rc2dgi_do_phase returns
+    RC2DGI_E_DEVICE (-7), names the chain, and the context falls back to one launch per level -- the following
+    frame is bit-identical to the unchained one.  (rc2dgi_compose: tests/test_present_gpu.py covers the display.)
+    The diagnostic knob rc_chain_spin -1 makes every wait time out at once (the product bound is 2^20 polls)."""
     from radiancecascade2dglobalillumination_amd import RC2DGIError
 
     W, H, N = 1200, 900, 6  # C1, where the committed schedule turns the chain on
     color, emis = make_scene("demo", W, H)
     ctx = RC2DGI(W, H, cascade_count=N, ray_range=2.0)
+    if report == "download_level":  # (the kept levels of a chained frame are the chain's own stores)
+        ctx.set_keep_levels(True)
     ctx.upload("color", color)
     ctx.upload("emissive", emis)
     ctx.do_rc2dgi()
@@ -827,11 +838,16 @@ def test_cascade_chain_timeout_is_an_error(RC2DGI, report):
             ctx.sync()
         elif report == "download":
             ctx.download("color")
-        else:  # (the frame has completed; rc2dgi_do itself does not synchronise)
+        elif report == "download_level":
+            ctx.download_level(0)
+        else:  # (the frame has completed; rc2dgi_do / rc2dgi_do_phase themselves do not synchronise)
             import torch
 
             torch.cuda.synchronize()
-            ctx.do_rc2dgi()
+            if report == "do":
+                ctx.do_rc2dgi()
+            else:
+                ctx.do_phase(1)
     assert ei.value.code == -7 and "cascade chain" in str(ei.value)
     assert ctx.get_tuning("rc_chain") == 0  # the fallback
     assert ctx.get_tuning("rc_chain_timeouts") > 0

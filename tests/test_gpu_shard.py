@@ -215,3 +215,46 @@ def test_group_shards_other_storage(R, storage):
         y0, y1 = c.shard_rows()
         assert np.array_equal(c.download("color")[y0:y1], want[y0:y1])
         c.close()
+
+
+def test_top_level_variant_on_strip_table_shards(R):
+    """Variant 25 (k_rc_top) at the top level of row-strip shards on strip tables, the smallest such frame (4096^2):
+    those shards hold no record texture, so a hit in a cell whose palette overflowed takes its record derived from
+    colorRT / emissiveRT, as every other variant does there.  The speckled scene overflows the palettes (asserted
+    below on the inputs).  Each shard's own rows equal the unsharded frame on its default schedule -- results do not
+    depend on the variant, so that is an independent reference."""
+    W = H = 4096
+    N, rr, blur, world = 6, 2.0, 1.5, 4
+    color, emis = _scene("speckled", W, H)
+    # a 64 x 64-texel cell with more than 16 distinct non-zero colours: its palette (16 entries) has no room
+    occ = np.any(color[..., :3] > 0, axis=-1)
+    cells = occ.reshape(H // 64, 64, W // 64, 64).sum(axis=(1, 3))
+    cj, ci = np.unravel_index(np.argmax(cells), cells.shape)
+    cell = color[cj * 64:cj * 64 + 64, ci * 64:ci * 64 + 64, :3].reshape(-1, 3)
+    distinct = np.unique(cell[np.any(cell > 0, axis=-1)], axis=0)
+    assert len(distinct) > 16, f"cell ({cj}, {ci}) holds {len(distinct)} colours: no palette overflows"
+    want = _full(R, W, H, N, rr, 1.0, blur, color, emis)
+    ctxs = []
+    for k in range(world):
+        c = R.RC2DGI(W, H, cascade_count=N, ray_range=rr)
+        c.set_shader_value("_BlurRadius", blur)
+        c.set_shard(k, world)
+        c.set_tuning("poison", 1)
+        c.set_tuning(f"rc_variant_L{N - 1}", 25)
+        c.upload("color", color)
+        c.upload("emissive", emis)
+        ctxs.append(c)
+    R.do_group(ctxs)
+    for c in ctxs:
+        c.sync()
+    for c in ctxs:
+        y0, y1 = c.shard_rows()
+        assert c.get_tuning("strip_tables_active") == 1
+        assert c.get_tuning(f"rc_variant_L{N - 1}") == 25
+        assert c.get_tuning("cascade_banded") == 0
+        for k in ("color", "temp", "blur", "final_gi"):
+            got = c.download(k)[y0:y1]
+            assert np.array_equal(got.view(np.uint8), want[k][y0:y1].view(np.uint8)), \
+                f"shard {(y0, y1)} {k}: {np.count_nonzero(got != want[k][y0:y1])} values differ"
+    for c in ctxs:
+        c.close()
