@@ -351,7 +351,11 @@ int rc2dgi_paint(rc2dgi_ctx *ctx, int which, const unsigned char *clear_rgba, co
  *   - rc2dgi_shard_connect: an RCCL communicator owned by the context (one process per GPU,
  *     ranks = shards); rc2dgi_do then runs the frame with the exchange (ncclBroadcast of each
  *     strip, grouped) on the context stream.  rc2dgi_shard_unique_id makes the id on rank 0;
- *     the host passes it to the other ranks.
+ *     the host passes it to the other ranks.  The transport library is librccl.so.1, opened at the
+ *     first of these calls in the process; the environment variable RC2DGI_RCCL_LIB, read once at that
+ *     moment, names a library to open instead (it must export the nine nccl* entry points used here;
+ *     the tests name a stand-in, tests/fake_rccl.cpp).  A named library that does not load or lacks a
+ *     symbol makes these calls return RC2DGI_E_UNSUPPORTED: there is no fallback to librccl.
  *   - rc2dgi_do_group: n contexts of one process, context k = shard k of n (any devices):
  *     phase 1 on each, strips exchanged by device copies, phase 2 on each.
  *   - rc2dgi_do_phase(ctx, 1 | 2) on an unsharded context (world 1) runs the two halves of a

@@ -78,6 +78,25 @@ def build(force: bool = False, verbose: bool = False, extra=(), out: str = LIB) 
     return out
 
 
+FAKE_RCCL_SRC = os.path.join(ROOT, "tests", "fake_rccl.cpp")
+FAKE_RCCL_LIB = os.path.join(ROOT, "tests", "libfake_rccl.so")
+
+
+def build_fake_rccl(out: str = FAKE_RCCL_LIB, force: bool = False) -> str:
+    """The test-only stand-in for RCCL (tests/fake_rccl.cpp; RC2DGI_RCCL_LIB names it): host code on the HIP runtime
+    API, linked like librc2dgi.so so that it binds to the HIP runtime already in the process.  Its internals are
+    hidden and it is linked -Bsymbolic: a process that also holds the real RCCL interposes nothing."""
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= os.path.getmtime(FAKE_RCCL_SRC):
+        return out
+    cmd = [hipcc(), "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall", "-Wextra",
+           "-Wl,-Bsymbolic", "-o", out + ".tmp", FAKE_RCCL_SRC, "-lpthread"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"hipcc failed on {FAKE_RCCL_SRC}:\n{r.stderr[-4000:]}")
+    os.replace(out + ".tmp", out)
+    return out
+
+
 if __name__ == "__main__":
     import sys
 

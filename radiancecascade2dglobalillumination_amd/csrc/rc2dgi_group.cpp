@@ -2,12 +2,16 @@
 // in-process group frame (rc2dgi_do_group) and the shard / plan entry points of the C ABI.
 #include <dlfcn.h>
 
+#include <cstdlib>
+
 #include "rc2dgi_ctx.h"
 
 namespace {
 
 // RCCL, resolved at first use (the single-GPU path never loads it).  In a process that already
-// loaded RCCL (e.g. through torch.distributed) dlopen returns that same library.
+// loaded RCCL (e.g. through torch.distributed) dlopen returns that same library.  RC2DGI_RCCL_LIB, read at that
+// first use, names the library to open instead (a test transport: tests/fake_rccl.cpp); if it does not load or
+// lacks a symbol the transport is unsupported -- never a fallback to librccl.
 struct Rccl {
   decltype(&ncclGetUniqueId) get_unique_id = nullptr;
   decltype(&ncclCommInitRank) comm_init_rank = nullptr;
@@ -24,8 +28,13 @@ struct Rccl {
 const Rccl &rccl() {
   static Rccl r = [] {
     Rccl x;
-    void *h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
+    void *h = nullptr;
+    if (const char *named = std::getenv("RC2DGI_RCCL_LIB"); named && *named) {
+      h = dlopen(named, RTLD_NOW | RTLD_LOCAL);
+    } else {
+      h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
+      if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
+    }
     if (!h) return x;
     x.get_unique_id = reinterpret_cast<decltype(x.get_unique_id)>(dlsym(h, "ncclGetUniqueId"));
     x.comm_init_rank = reinterpret_cast<decltype(x.comm_init_rank)>(dlsym(h, "ncclCommInitRank"));
@@ -77,11 +86,12 @@ int jfa_exchange_rccl(rc2dgi_ctx *c, int t) {
   const Rccl &R = rccl();
   const size_t rowb = (size_t)c->sd.pitch * sizeof(unsigned);
   ncclResult_t e = R.group_start();
+  hipError_t he = hipSuccess;  // (a failing self-copy still closes the group below)
   for (const JfaXfer &x : c->jx.steps[t].xfers) {
-    if (e != ncclSuccess) break;
+    if (e != ncclSuccess || he != hipSuccess) break;
     if (x.src == c->rank && x.dst == c->rank) {
-      HIPCHK(c, hipMemcpyAsync(jfa_xbuf(c, t, x.dst_buf, x.dst_row), jfa_xbuf(c, t, 0, x.src_row), x.rows * rowb,
-                               hipMemcpyDeviceToDevice, c->stream));
+      he = hipMemcpyAsync(jfa_xbuf(c, t, x.dst_buf, x.dst_row), jfa_xbuf(c, t, 0, x.src_row), x.rows * rowb,
+                          hipMemcpyDeviceToDevice, c->stream);
     } else if (x.src == c->rank) {
       e = R.send(jfa_xbuf(c, t, 0, x.src_row), x.rows * rowb, ncclUint8, x.dst, c->comm, c->stream);
     } else if (x.dst == c->rank) {
@@ -90,6 +100,7 @@ int jfa_exchange_rccl(rc2dgi_ctx *c, int t) {
   }
   const ncclResult_t e2 = R.group_end();
   if (e == ncclSuccess) e = e2;
+  if (he != hipSuccess) return hip_fail(c, he, "hipMemcpyAsync (JumpFlood exchange, own rows)");
   if (e != ncclSuccess) return fail(c, RC2DGI_E_HIP, std::string("JumpFlood exchange: ") + R.error_string(e));
   return RC2DGI_OK;
 }

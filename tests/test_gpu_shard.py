@@ -2,14 +2,16 @@
 
 In-process shards (``rc2dgi_do_group``: context k = shard k of n, distRT strips exchanged by
 device copies) on one GPU, with every intermediate render texture poisoned before the frame;
-each shard's colorRT / tempRT strip must equal the whole-frame result bit for bit.  The RCCL
-transport is exercised at world size 1 (communicator, grouped in-place broadcast); more ranks
-need more GPUs than a test box has.
+each shard's colorRT / tempRT strip must equal the whole-frame result bit for bit.  The real RCCL
+is exercised at world size 1 here (communicator, grouped in-place broadcast); rc2dgi_do over a
+communicator at world 2 to 8 runs in test_gpu_rccl_ranks.py, its ranks as threads of one process
+over a stand-in transport with RCCL's calling semantics (fake_rccl.cpp).
 """
 import numpy as np
 import pytest
 
 from conftest import rel_err  # noqa: F401  (shared helpers live there)
+from shard_compare import assert_shard_matches_whole, whole_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -37,13 +39,7 @@ def _scene(spec, W, H):
 
 
 def _full(R, W, H, N, rr, rs, blur, color, emis):
-    ctx = R.RC2DGI(W, H, cascade_count=N, render_scale=rs, ray_range=rr)
-    ctx.set_shader_value("_BlurRadius", blur)
-    ctx.frame(color, emis)
-    ctx.sync()
-    out = {k: ctx.download(k) for k in ("color", "temp", "dist", "jump1", "jump2", "blur", "final_gi")}
-    ctx.close()
-    return out
+    return whole_frame(R, W, H, N, rr, rs, blur, color, emis)
 
 
 CASES = [
@@ -81,33 +77,7 @@ def test_group_shards_match_whole_frame(R, W, H, N, rr, rs, blur, world, scene):
         for c in ctxs:
             c.sync()
         for c in ctxs:
-            y0, y1 = c.shard_rows()
-            # the merged strip, the JumpFlood textures' own rows (computed on the strip windows with
-            # the row exchange) and the whole distance field (all-gathered)
-            for k in ("color", "temp", "jump1", "jump2"):
-                got = c.download(k)[y0:y1]
-                mism = np.count_nonzero(got != want[k][y0:y1])
-                assert mism == 0, f"shard {c.shard_rows()} {k}: {mism} values differ"
-            # the whole distance field (all-gathered) -- with strip tables the shards exchange the march field
-            # instead, and distRT holds the own rows
-            # cascadeBlurRT and the blurred final GI (cascades the size of the screen): the own rows; on the fused blur + merge
-            # (power-of-two sizes) the shard holds only those (strip-sized textures)
-            if c.cascade_resolution == (W, H) and blur > 0:
-                for k in ("blur", "final_gi"):
-                    got = c.download(k)[y0:y1]
-                    mism = np.count_nonzero(got != want[k][y0:y1])
-                    assert mism == 0, f"shard {c.shard_rows()} {k}: {mism} values differ"
-            pow2 = (W & (W - 1)) == 0 and (H & (H - 1)) == 0
-            assert c.get_tuning("blur_strip_sized") == (pow2 and c.cascade_resolution == (W, H) and 0 < blur < 3)
-            st = c.get_tuning("strip_tables_active")
-            assert st == (W == H and W >= 4096), (W, H, st)
-            # strip tables on the fused blur + merge: giRT1 / giRT2 hold the shard's band of every direction block
-            assert c.get_tuning("cascade_banded") == (st and blur > 0), (W, H, blur)
-            d = c.download("dist")
-            if st:
-                assert np.array_equal(d[y0:y1], want["dist"][y0:y1]), f"shard {c.shard_rows()}: distRT rows"
-            else:
-                assert np.array_equal(d, want["dist"]), f"shard {c.shard_rows()}: distRT"
+            assert_shard_matches_whole(c, want, W, H, blur, expect_strip_tables=(W == H and W >= 4096))
     for c in ctxs:
         c.close()
 
