@@ -83,7 +83,7 @@ void free_buffers(rc2dgi_ctx *c) {
   void *bufs[] = {c->color_in, c->emissive, c->temp, c->color_out, c->jump1, c->jump2, c->dist, c->occ,
                   c->gi1,      c->gi2,      c->blur, c->dirs,      c->sky, c->gi_spare, c->dist_t, c->dist_p, c->dist_n, c->shade,
                   c->cmin,     c->dexit, c->hitc, c->dclr, c->dboxes, c->mfield, c->cell_pal, c->shade_list, c->jtail,
-                  c->tc, c->bconst};
+                  c->tc, c->bconst, c->odd_flag};
   for (void *p : bufs)
     if (p) (void)hipFree(p);
   for (unsigned *&b : c->jblk) {
@@ -105,6 +105,7 @@ void free_buffers(rc2dgi_ctx *c) {
   c->jtail = nullptr;
   c->tc = nullptr;
   c->bconst = nullptr;
+  c->odd_flag = nullptr;
   c->built_hitc = c->built_cmin = c->built_dclr = c->built_pal = false;
   c->dboxes = nullptr;
   c->gi1 = c->gi2 = c->blur = c->gi_spare = nullptr;

@@ -312,6 +312,21 @@ static int blur_and_merge(rc2dgi_ctx *c, const FramePlan &plan, float4 *&finalGI
     bool fused = false;
     BlurTaps bt;
     const bool mrg = c->sd.W == c->CW && c->sd.H == c->CH && !c->linux_merge;
+    // The fused kernels skip LINEAR taps of weight 0, an identity but for non-finite or huge neighbours
+    // (absmax4, rc2dgi_kernels.hip): they report such a value through odd_flag, and the frame is then redone tap by tap
+    // on the device (launch_blur_exact below; one launch that returns at once otherwise).  Whole frames only: a
+    // row-strip shard stages its own rows, so it neither sees every value nor holds every row the redo reads.
+    unsigned *flag = nullptr;
+    if (c->world == 1 && !c->gwin && !c->gband) {
+      if (!c->odd_flag) {
+        HIPCHK(c, alloc(&c->odd_flag, sizeof(unsigned)));
+        HIPCHK(c, hipMemsetAsync(c->odd_flag, 0, sizeof(unsigned), st));
+        c->odd_epoch = 0;
+      }
+      if (++c->odd_epoch == 0) c->odd_epoch = 1;  // (0: the cleared flag)
+      flag = c->odd_flag;
+    }
+    const unsigned epoch = c->odd_epoch;
     // a fused kernel writes the copied-back GI into gi_spare, which then becomes finalGI: only when
     // every launch of it ran (a refused launch -- shapes it does not take -- falls back before any
     // launch ran, since the shapes are the same for every row interval)
@@ -320,7 +335,7 @@ static int blur_and_merge(rc2dgi_ctx *c, const FramePlan &plan, float4 *&finalGI
       for (auto &r : plan.blur.iv)
         ok = ok && launch_blur_rows(finalGI, c->blur, c->gi_spare, c->cd, c->blur_radius, c->color_in, c->temp,
                                     c->color_out, c->sd, mrg, st, r.first, r.second, c->ow0, c->ow1,
-                                    c->gband ? c->gb0[0] : 0, c->gband ? c->gbn[0] : 0);
+                                    c->gband ? c->gb0[0] : 0, c->gband ? c->gbn[0] : 0, flag, epoch);
       if (!ok && plan.blur.iv.size() > 1) return fail(c, RC2DGI_E_HIP, "fixed-tap blur refused a row interval");
       fused = ok;
       merged = ok && mrg;
@@ -331,12 +346,16 @@ static int blur_and_merge(rc2dgi_ctx *c, const FramePlan &plan, float4 *&finalGI
     if (!fused && c->blur_path <= 1 && blur_fused_ok(c->cd, c->blur_radius)) {
       bool ok = true;
       for (auto &r : plan.blur.iv)
-        ok = ok && launch_blur_fused(finalGI, c->blur, c->gi_spare, c->cd, c->blur_radius, st, r.first, r.second);
+        ok = ok && launch_blur_fused(finalGI, c->blur, c->gi_spare, c->cd, c->blur_radius, st, r.first, r.second,
+                                     flag, epoch);
       if (!ok && plan.blur.iv.size() > 1) return fail(c, RC2DGI_E_HIP, "LDS-tiled blur refused a row interval");
       fused = ok;
     }
     if (fused) {
       HIPCHK(c, hipGetLastError());
+      if (flag)
+        HIPCHK(c, launch_blur_exact(flag, epoch, finalGI, c->blur, c->gi_spare, c->cd, c->blur_radius, c->color_in,
+                                    c->temp, c->color_out, c->sd, merged, st));
       if (!c->gwin) std::swap(finalGI, c->gi_spare);  // (gwin: the final GI stays in the strip-sized gi_spare)
     } else {
       for (auto &r : plan.blur.iv) HIPCHK(c, launch_blur(finalGI, c->blur, c->cd, c->blur_radius, st, r.first, r.second));

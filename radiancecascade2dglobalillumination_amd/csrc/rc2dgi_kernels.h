@@ -303,8 +303,16 @@ hipError_t launch_blur_copyback(const float4 *blur, float4 *gi, CascadeDims c, h
 // both in one pass (power-of-two cascade sizes, radius <= 6); gi_out may not alias gi_in.
 // Returns false (nothing launched) when the shape is not supported.
 bool blur_fused_ok(CascadeDims c, float radius);  // power-of-two sizes, radius <= 6
+// (flag: set to `epoch` when a value met breaks the identities the fused kernels rest on -- see absmax4 in
+// rc2dgi_kernels.hip; nullptr: not reported)
 bool launch_blur_fused(const float4 *gi_in, float4 *blur_out, float4 *gi_out, CascadeDims c, float radius,
-                       hipStream_t st, int row0 = 0, int row1 = -1);
+                       hipStream_t st, int row0 = 0, int row1 = -1, unsigned *flag = nullptr, unsigned epoch = 0);
+// what launch_blur + launch_blur_copyback (+ launch_merge when `merge`) leave, from gi_in alone into blur_out / gi_out
+// (/ temp / color_out), on the device's say: the kernel returns at once unless *flag == epoch.  Whole frames of
+// power-of-two cascades; gi_out may not alias gi_in.
+hipError_t launch_blur_exact(const unsigned *flag, unsigned epoch, const float4 *gi_in, float4 *blur_out, float4 *gi_out,
+                             CascadeDims c, float radius, const float4 *color_in, float4 *temp, float4 *color_out,
+                             ScreenDims s, bool merge, hipStream_t st);
 
 // Blur + copy-back (+ merge and its copy-back when `merge`) with fixed taps; false when the
 // radius / sizes do not allow it (see k_blur_rows).  blur_rows_plan: F = floor(radius) or -1.
@@ -314,7 +322,8 @@ int blur_rows_plan(CascadeDims c, float radius, BlurTaps *bt);
 // gn cascade rows from g0 on, cyclically -- a shard's banded level 0; gn <= 0: every row)
 bool launch_blur_rows(const float4 *gi_in, float4 *blur_out, float4 *gi_out, CascadeDims c, float radius,
                       const float4 *color_in, float4 *temp, float4 *color_out, ScreenDims s, bool merge,
-                      hipStream_t st, int row0 = 0, int row1 = -1, int m0 = 0, int m1 = -1, int g0 = 0, int gn = 0);
+                      hipStream_t st, int row0 = 0, int row1 = -1, int m0 = 0, int m1 = -1, int g0 = 0, int gn = 0,
+                      unsigned *flag = nullptr, unsigned epoch = 0);
 
 // merge.fs into temp, then tempRT -> colorRT copy-back (RC2DGI.cs:389-404); linux_merge: raylib's default
 // shader in place of merge.fs (RC2DGI_FLAG_LINUX_MERGE_FALLBACK)

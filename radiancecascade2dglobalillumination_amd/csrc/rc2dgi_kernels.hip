@@ -1172,6 +1172,20 @@ __global__ __launch_bounds__(256) void k_blur(const typename GI::T *__restrict__
   GI::RT::st(&blur_out[(size_t)j * c.pitch + i], GI::RT::blend_black(res));  // cascadeBlurRT cleared to (0,0,0,1)
 }
 
+// The fused blur kernels below skip LINEAR taps of weight 0: fma(0, b - a, a) = a.  That holds for finite a, b whose
+// difference is finite; the reference's lerp gives NaN when the neighbour is not finite (0 * inf).  A G_0 channel
+// that is not finite, or 2^30 or more in magnitude, could break the identity in a lerp downstream; below that every
+// value of the pass stays finite (the blur is a convex sum of G_0 values, so below 2^30 too; its blend over black
+// and the copy-back multiply two such and add: below 2^62, then 2^124; the merge adds colour).  absmax4 is the
+// largest magnitude of a texel as bits (NaN and inf compare above every finite value); a fused kernel that stages a
+// texel at or above kOddBits writes the frame's epoch to *flag, and k_blur_exact then redoes the frame tap by tap
+// (launch_blur_exact).  Every G_0 texel is staged by some workgroup of a whole frame.
+constexpr unsigned kOddBits = 0x4E800000u;  // 2^30
+__device__ __forceinline__ unsigned absmax4(float4 v) {
+  return max(max(__float_as_uint(v.x) & 0x7FFFFFFFu, __float_as_uint(v.y) & 0x7FFFFFFFu),
+             max(__float_as_uint(v.z) & 0x7FFFFFFFu, __float_as_uint(v.w) & 0x7FFFFFFFu));
+}
+
 // Blur.fs + its blended copy-back in one pass, for power-of-two cascade sizes.  There the
 // copy-back's LINEAR sample of cascadeBlurRT at fragTexCoord lands exactly on the texel
 // (x = (i+0.5)/n*n - 0.5 = i, weight 0: fma(0, b - a, a) = a), so each texel needs only its
@@ -1181,15 +1195,18 @@ template <int H, class GI>
 __global__ __launch_bounds__(256) void k_blur_fused(const typename GI::T *__restrict__ gi_in,
                                                     float4 *__restrict__ blur_out, typename GI::T *__restrict__ gi_out,
                                                     CascadeDims c, float radius,
-                                                    int tile0) {
+                                                    int tile0, unsigned *__restrict__ flag, unsigned epoch) {
   constexpr int TW = 64 + 2 * H, TH = 16 + 2 * H;
   __shared__ float4 tile[TH * TW];
   const int by = (int)blockIdx.y + tile0;  // 16-row tile
   const int x0 = blockIdx.x * 64 - H, y0 = by * 16 - H;
+  unsigned odd = 0u;
   for (int k = threadIdx.x; k < TW * TH; k += 256) {
     const int ty = k / TW, tx = k - ty * TW;
     const int gx = (x0 + tx) & (c.CW - 1), gy = (y0 + ty) & (c.CH - 1);
-    tile[k] = GI::ld(&gi_in[(size_t)gy * c.pitch + gx]);
+    const float4 g = GI::ld(&gi_in[(size_t)gy * c.pitch + gx]);
+    tile[k] = g;
+    odd = max(odd, absmax4(g));
   }
   __syncthreads();
   const Axis ax{c.CW, 1}, ay{c.CH, 1};
@@ -1257,8 +1274,10 @@ __global__ __launch_bounds__(256) void k_blur_fused(const typename GI::T *__rest
     const float4 b = blend_over_black(res);  // cascadeBlurRT cleared to (0,0,0,1)
     const size_t o = (size_t)j * c.pitch + i;
     blur_out[o] = b;
-    GI::st(&gi_out[o], blend(b, tile[(j - y0) * TW + (i - x0)]));  // copy-back onto finalGI, blended
+    const float4 g = GI::round(blend(b, tile[(j - y0) * TW + (i - x0)]));  // copy-back onto finalGI, blended
+    GI::st(&gi_out[o], g);
   }
+  if (odd >= kOddBits && flag) *flag = epoch;
 }
 
 // Blur.fs + blended copy-back (+ merge.fs and its copy-back when MERGE) for power-of-two cascades
@@ -1281,18 +1300,21 @@ __global__ __launch_bounds__(256) void k_blur_rows(const typename GI::T *__restr
                                                    CascadeDims c, BlurTaps bt,
                                                    const float4 *__restrict__ color_in, float4 *__restrict__ temp,
                                                    float4 *__restrict__ color_out, int spitch, int tile0, int m0, int m1,
-                                                   int g0, int gn) {
+                                                   int g0, int gn, unsigned *__restrict__ flag, unsigned epoch) {
   constexpr int RPT = RC2DGI_BLUR_RPT, TR = 4 * RPT;  // rows per thread, rows per tile
   constexpr int HALO = F + 1, TW = 64 + 2 * HALO, TH = TR + 2 * HALO, NR = RPT + 2 * HALO;
   __shared__ float4 tile[TH * TW];
   const int by = (int)blockIdx.y + tile0;  // TR-row tile
   const int x0 = blockIdx.x * 64 - HALO, y0 = by * TR - HALO;
+  unsigned odd = 0u;  // (absmax4: at kOddBits and above a skipped weight-0 tap is no identity)
   for (int k = threadIdx.x; k < TW * TH; k += 256) {
     const int ty = k / TW, tx = k - ty * TW;
     // gi_in holds rows [g0, g0 + gn) cyclically (a row-strip shard's banded level 0; else g0 0, gn CH): the band
     // row, rows past the band read its last row (only for texels the launch does not store)
     const int gx = (x0 + tx) & (c.CW - 1), gy = min((y0 + ty - g0) & (c.CH - 1), gn - 1);
-    tile[k] = GI::ld(&gi_in[(size_t)gy * c.pitch + gx]);
+    const float4 g = GI::ld(&gi_in[(size_t)gy * c.pitch + gx]);
+    tile[k] = g;
+    odd = max(odd, absmax4(g));
   }
   __syncthreads();
   const int lx = (threadIdx.x & 63) + HALO;  // tile column of this thread's texel
@@ -1360,6 +1382,7 @@ __global__ __launch_bounds__(256) void k_blur_rows(const typename GI::T *__restr
       color_out[mo] = blend(tt, col);
     }
   }
+  if (odd >= kOddBits && flag) *flag = epoch;
 }
 
 template <class GI>
@@ -1395,6 +1418,73 @@ __global__ __launch_bounds__(256) void k_merge(const float4 *__restrict__ color_
   const float4 t = GI::RT::blend_black(src);  // tempRT as cleared by ClearAllRTs
   temp[mo] = t;
   color_out[mo] = GI::RT::blend(t, col);      // tempRT -> colorRT, default shader, blended
+}
+
+// The fused blur kernels' frame redone tap by tap, for a frame in which one of them staged such a value (*flag ==
+// epoch; otherwise every workgroup returns at once).  Each texel evaluates k_blur, k_blur_copyback and (MERGE)
+// k_merge as they are written -- the blur of every texel in its copy-back's LINEAR footprint, the copied-back GI of
+// every texel in the merge's footprint -- from G_0 alone, so no pass waits for another.  Slow (nothing is shared
+// between texels or footprints: 5 blur texels of 9 taps each, 21 with MERGE) and rare.  Whole frames only: no shard
+// windows, no banded G_0.  A workgroup strides over the rows (a small grid: the launch costs little when it is idle).
+template <bool MERGE, class GI>
+__global__ __launch_bounds__(256) void k_blur_exact(const unsigned *__restrict__ flag, unsigned epoch,
+                                                    const typename GI::T *__restrict__ gi_in,
+                                                    float4 *__restrict__ blur_out, typename GI::T *__restrict__ gi_out,
+                                                    CascadeDims c, float radius, const float4 *__restrict__ color_in,
+                                                    float4 *__restrict__ temp, float4 *__restrict__ color_out,
+                                                    ScreenDims s) {
+  if (*flag != epoch) return;
+  const int i = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (i >= c.CW) return;
+  const Axis ax{c.CW, c.powW}, ay{c.CH, c.powH};
+  const float tsx = 1.0f / (float)c.CW, tsy = 1.0f / (float)c.CH;
+  auto blur_at = [&](int x, int y) {  // k_blur's texel (x, y)
+    const float u = texcoord(x, ax), v = texcoord(y, ay);
+    const float kx[9] = {-1.f, 1.f, -1.f, 1.f, 0.f, 0.f, -1.f, 1.f, 0.f};
+    const float ky[9] = {-1.f, -1.f, 1.f, 1.f, -1.f, 1.f, 0.f, 0.f, 0.f};
+    float4 res = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll 1
+    for (int k = 0; k < 9; ++k) {
+      float su = u, sv = v, w = 0.250f;
+      if (k < 8) {
+        su = u + (kx[k] * tsx) * radius;
+        sv = v + (ky[k] * tsy) * radius;
+        w = k < 4 ? 0.0625f : 0.125f;
+      }
+      const float4 t = sample_bilinear_gi<GI>(gi_in, c.pitch, ax, ay, su, sv);
+      res.x = res.x + t.x * w;
+      res.y = res.y + t.y * w;
+      res.z = res.z + t.z * w;
+      res.w = res.w + t.w * w;
+    }
+    return GI::RT::blend_black(res);
+  };
+  auto gi_at = [&](int x, int y) {  // k_blur_copyback's texel (x, y), as it reads back
+    int xa, xb, ya, yb;
+    float wx, wy;
+    wrap_linear(texcoord(x, ax), ax, xa, xb, wx);
+    wrap_linear(texcoord(y, ay), ay, ya, yb, wy);
+    const float4 sm = GI::RT::bilerp(blur_at(xa, ya), blur_at(xb, ya), blur_at(xa, yb), blur_at(xb, yb), wx, wy);
+    return GI::round(GI::blend(sm, GI::ld(&gi_in[(size_t)y * c.pitch + x])));
+  };
+  for (int j = blockIdx.y * 4 + (threadIdx.x >> 6); j < c.CH; j += 4 * (int)gridDim.y) {
+    const size_t o = (size_t)j * c.pitch + i;
+    blur_out[o] = blur_at(i, j);
+    GI::st(&gi_out[o], gi_at(i, j));
+    if constexpr (MERGE) {  // k_merge (cascade == screen)
+      int xa, xb, ya, yb;
+      float wx, wy;
+      wrap_linear(texcoord(i, Axis{s.W, s.powW}), ax, xa, xb, wx);
+      wrap_linear(texcoord(j, Axis{s.H, s.powH}), ay, ya, yb, wy);
+      const float4 g = GI::bilerp(gi_at(xa, ya), gi_at(xb, ya), gi_at(xa, yb), gi_at(xb, yb), wx, wy);
+      const size_t so = (size_t)j * s.pitch + i;
+      const float4 col = color_in[so];
+      const float4 src = make_float4(fminf(col.x + g.x, 1.0f), fminf(col.y + g.y, 1.0f), fminf(col.z + g.z, 1.0f), col.w);
+      const float4 t = GI::RT::blend_black(src);
+      temp[so] = t;
+      color_out[so] = GI::RT::blend(t, col);
+    }
+  }
 }
 
 __global__ __launch_bounds__(256) void k_unorm8_to_f32(const unsigned char *__restrict__ src, int src_pitch,
@@ -2173,7 +2263,7 @@ bool blur_fused_ok(CascadeDims c, float radius) {
 }
 
 bool launch_blur_fused(const float4 *gi_in, float4 *blur_out, float4 *gi_out, CascadeDims c, float radius,
-                       hipStream_t st, int row0, int row1) {
+                       hipStream_t st, int row0, int row1, unsigned *flag, unsigned epoch) {
   if (!blur_fused_ok(c, radius)) return false;
   clamp_rows(c.CH, row0, row1);
   if (row0 >= row1) return true;
@@ -2183,14 +2273,18 @@ bool launch_blur_fused(const float4 *gi_in, float4 *blur_out, float4 *gi_out, Ca
   auto *g16o = reinterpret_cast<GiF16::T *>(gi_out);
   if (radius <= 2.0f) {
     if (c.gi_f16)
-      hipLaunchKernelGGL((k_blur_fused<4, GiF16>), grid, dim3(256), 0, st, g16i, blur_out, g16o, c, radius, t0);
+      hipLaunchKernelGGL((k_blur_fused<4, GiF16>), grid, dim3(256), 0, st, g16i, blur_out, g16o, c, radius, t0, flag,
+                         epoch);
     else
-      hipLaunchKernelGGL((k_blur_fused<4, GiF32>), grid, dim3(256), 0, st, gi_in, blur_out, gi_out, c, radius, t0);
+      hipLaunchKernelGGL((k_blur_fused<4, GiF32>), grid, dim3(256), 0, st, gi_in, blur_out, gi_out, c, radius, t0,
+                         flag, epoch);
   } else if (radius <= 6.0f) {
     if (c.gi_f16)
-      hipLaunchKernelGGL((k_blur_fused<8, GiF16>), grid, dim3(256), 0, st, g16i, blur_out, g16o, c, radius, t0);
+      hipLaunchKernelGGL((k_blur_fused<8, GiF16>), grid, dim3(256), 0, st, g16i, blur_out, g16o, c, radius, t0, flag,
+                         epoch);
     else
-      hipLaunchKernelGGL((k_blur_fused<8, GiF32>), grid, dim3(256), 0, st, gi_in, blur_out, gi_out, c, radius, t0);
+      hipLaunchKernelGGL((k_blur_fused<8, GiF32>), grid, dim3(256), 0, st, gi_in, blur_out, gi_out, c, radius, t0,
+                         flag, epoch);
   }
   else
     return false;
@@ -2210,7 +2304,8 @@ int blur_rows_plan(CascadeDims c, float radius, BlurTaps *bt) {
 
 bool launch_blur_rows(const float4 *gi_in, float4 *blur_out, float4 *gi_out, CascadeDims c, float radius,
                       const float4 *color_in, float4 *temp, float4 *color_out, ScreenDims s, bool merge,
-                      hipStream_t st, int row0, int row1, int m0, int m1, int g0, int gn) {
+                      hipStream_t st, int row0, int row1, int m0, int m1, int g0, int gn, unsigned *flag,
+                      unsigned epoch) {
   BlurTaps bt;
   if (m1 < 0) m1 = s.H;
   if (gn <= 0) {
@@ -2230,10 +2325,10 @@ bool launch_blur_rows(const float4 *gi_in, float4 *blur_out, float4 *gi_out, Cas
     if (c.gi_f16)                                                                                              \
       hipLaunchKernelGGL((k_blur_rows<FV, MV, GiF16>), grid, dim3(256), 0, st,                                 \
                          reinterpret_cast<const GiF16::T *>(gi_in), blur_out, reinterpret_cast<GiF16::T *>(gi_out), \
-                         c, bt, color_in, temp, color_out, s.pitch, t0, m0, m1, g0, gn);                        \
+                         c, bt, color_in, temp, color_out, s.pitch, t0, m0, m1, g0, gn, flag, epoch);           \
     else                                                                                                       \
       hipLaunchKernelGGL((k_blur_rows<FV, MV, GiF32>), grid, dim3(256), 0, st, gi_in, blur_out, gi_out, c, bt,  \
-                         color_in, temp, color_out, s.pitch, t0, m0, m1, g0, gn);                               \
+                         color_in, temp, color_out, s.pitch, t0, m0, m1, g0, gn, flag, epoch);                  \
   } while (0)
   if (merge) {
     if (F == 0) RC2DGI_BLUR_ROWS(0, true); else if (F == 1) RC2DGI_BLUR_ROWS(1, true); else RC2DGI_BLUR_ROWS(2, true);
@@ -2242,6 +2337,26 @@ bool launch_blur_rows(const float4 *gi_in, float4 *blur_out, float4 *gi_out, Cas
   }
 #undef RC2DGI_BLUR_ROWS
   return true;
+}
+
+hipError_t launch_blur_exact(const unsigned *flag, unsigned epoch, const float4 *gi_in, float4 *blur_out, float4 *gi_out,
+                             CascadeDims c, float radius, const float4 *color_in, float4 *temp, float4 *color_out,
+                             ScreenDims s, bool merge, hipStream_t st) {
+  if (c.gi_u8 || (merge && !(s.W == c.CW && s.H == c.CH))) return hipErrorInvalidValue;
+  const dim3 grid(ceil_div(c.CW, 64), min(ceil_div(c.CH, 4), 32));  // (k_blur_exact strides over the rows)
+#define RC2DGI_BLUR_EXACT(MV)                                                                                      \
+  do {                                                                                                             \
+    if (c.gi_f16)                                                                                                  \
+      hipLaunchKernelGGL((k_blur_exact<MV, GiF16>), grid, dim3(256), 0, st, flag, epoch,                           \
+                         reinterpret_cast<const GiF16::T *>(gi_in), blur_out, reinterpret_cast<GiF16::T *>(gi_out), \
+                         c, radius, color_in, temp, color_out, s);                                                 \
+    else                                                                                                           \
+      hipLaunchKernelGGL((k_blur_exact<MV, GiF32>), grid, dim3(256), 0, st, flag, epoch, gi_in, blur_out, gi_out,  \
+                         c, radius, color_in, temp, color_out, s);                                                 \
+  } while (0)
+  if (merge) RC2DGI_BLUR_EXACT(true); else RC2DGI_BLUR_EXACT(false);
+#undef RC2DGI_BLUR_EXACT
+  return hipGetLastError();
 }
 
 hipError_t launch_blur_copyback(const float4 *blur, float4 *gi, CascadeDims c, hipStream_t st, int row0, int row1) {
