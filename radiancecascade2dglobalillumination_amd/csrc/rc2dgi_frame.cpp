@@ -17,6 +17,13 @@ int jfa_launch(rc2dgi_ctx *c, const FramePlan &plan, int t) {
   jfa_offsets(c->W, c->H, t, ox, oy);  // vec2(x, y) * _Aspect.yx * _StepSize
   unsigned short *dist = t == c->S - 1 ? c->dist : nullptr;  // 3. DistanceField fused into the last step
   hipStream_t st = c->stream;
+  JfaStepArgs a;  // (what the step's launches share; a row-strip shard leaves lds, small_rt and jrows off)
+  a.first = t == 0;
+  a.dist = dist;
+  a.off_x = ox;
+  a.off_y = oy;
+  a.tc = c->tc;
+  a.tmode = jfa_tmode(c);
   if (!c->strip) {
     // the first four steps in one kernel (k_jfa_coset): the ScreenUV mask -> J_3
     const int lat = (c->jfa_coset == 2 && c->W <= 4096) ? 32 : 16;  // (the float-key build of lat 32 spills)
@@ -39,21 +46,30 @@ int jfa_launch(rc2dgi_ctx *c, const FramePlan &plan, int t) {
         HIPCHK(c, launch_jfa_tail(out_of(t - 1), jfa_out(c, c->S - 1), jfa_out(c, c->S - 2), c->dist, c->sd, c->S, nt, st));
       return RC2DGI_OK;
     }
-    unsigned *out = out_of(t);
-    const unsigned *src = t == 0 ? c->occ : out_of(t - 1);
-    for (auto &r : plan.jfa[t].iv)
-      HIPCHK(c, launch_jfa_step(t == 0, src, t == 0 ? c->mpitch : c->sd.pitch, out, dist, c->sd, ox, oy, st,
-                                r.first, r.second, nullptr, 0, c->jfa_lds, c->jfa_rt, c->jfa_rows, c->tc,
-                                jfa_tmode(c)));
+    a.src = t == 0 ? c->occ : out_of(t - 1);
+    a.src_pitch = t == 0 ? c->mpitch : c->sd.pitch;
+    a.dst = out_of(t);
+    a.lds = c->jfa_lds;
+    a.small_rt = c->jfa_rt;
+    a.jrows = c->jfa_rows;
+    for (auto &r : plan.jfa[t].iv) {
+      a.row0 = r.first;
+      a.row1 = r.second;
+      HIPCHK(c, launch_jfa_step(a, c->sd, st));
+    }
     return RC2DGI_OK;
   }
   // row-strip shard: the own strip, into its window (global row y0 - m = local row 0)
   int y0, y1;
   strip_rows(c->H, c->rank, c->world, y0, y1);
-  const int wrow0 = y0 - c->jx.m;
+  a.dst = jfa_out(c, t);
+  a.row0 = y0;
+  a.row1 = y1;
+  a.dst_row0 = y0 - c->jx.m;
   if (t == 0) {
-    HIPCHK(c, launch_jfa_step(true, c->occ, c->mpitch, jfa_out(c, 0), dist, c->sd, ox, oy, st, y0, y1, nullptr, wrow0,
-                              0, 1, 0, c->tc, jfa_tmode(c)));
+    a.src = c->occ;
+    a.src_pitch = c->mpitch;
+    HIPCHK(c, launch_jfa_step(a, c->sd, st));
     return RC2DGI_OK;
   }
   int buf[3], row0[3];
@@ -64,8 +80,9 @@ int jfa_launch(rc2dgi_ctx *c, const FramePlan &plan, int t) {
     win.base[y] = buf[y] == 0 ? jfa_out(c, t - 1) : c->jblk[buf[y] - 1];
     win.row0[y] = row0[y];
   }
-  HIPCHK(c, launch_jfa_step(false, nullptr, c->sd.pitch, jfa_out(c, t), dist, c->sd, ox, oy, st, y0, y1, &win, wrow0,
-                            0, 1, 0, c->tc, jfa_tmode(c)));
+  a.src_pitch = c->sd.pitch;  // (src stays nullptr: every tap row comes from the window)
+  a.window = &win;
+  HIPCHK(c, launch_jfa_step(a, c->sd, st));
   return RC2DGI_OK;
 }
 
@@ -183,6 +200,14 @@ int phase2_side(rc2dgi_ctx *c, SidePass &f) {
   c->built_dclr = mps;
   c->built_pal = pal;
   bool side = false, dc_merged = false;  // (k_dir_clear on the side stream / in k_shade_cells' launch)
+  ShadeCminArgs a;
+  a.dist = c->dist;
+  a.color = c->color_in;
+  a.emis = c->emissive;
+  a.shade = stt ? nullptr : c->shade;
+  a.reflectivity = c->reflectivity;
+  a.cmin = c->cmin;
+  a.hitc = mps ? c->hitc : nullptr;
   if (fused) {
     // (the split pass's parity advances only with the split passes themselves: k_shade_cells clears the other
     // parity's counter for the next one)
@@ -193,22 +218,24 @@ int phase2_side(rc2dgi_ctx *c, SidePass &f) {
     side = split && mps && !stt && c->side_overlap == 1 && c->side_stream && c->ev_fork && c->ev_join;
     // side_overlap 2: k_dir_clear's workgroups appended to k_shade_cells' grid instead (one launch, one stream)
     dc_merged = split && mps && !stt && c->side_overlap == 2;
-    int cr0 = 0, ncr = kCminDim;  // (strip tables: the cell rows of the own strip)
-    if (stt) {
+    a.mf = pal ? c->mfield : nullptr;
+    a.cpal = pal ? c->cell_pal : nullptr;
+    a.list = split ? c->shade_list : nullptr;
+    a.parity = split ? (int)(c->split_frames++ & 1u) : 0;
+    a.after_scan = side ? c->ev_fork : nullptr;
+    a.boxes = dc_merged ? c->dboxes : nullptr;
+    a.dclr = dc_merged ? c->dclr : nullptr;
+    if (stt) {  // (strip tables: the cell rows of the own strip)
       int y0, y1;
       strip_rows(c->H, c->rank, c->world, y0, y1);
       const int csh = dist_cmin_shift(c->W, c->H);
-      cr0 = y0 >> csh;
-      ncr = (y1 - y0) >> csh;
+      a.cr0 = y0 >> csh;
+      a.ncr = (y1 - y0) >> csh;
     }
-    HIPCHK(c, launch_shade_cmin(c->dist, c->color_in, c->emissive, stt ? nullptr : c->shade, c->sd, c->reflectivity,
-                                c->cmin, mps ? c->hitc : nullptr, st, pal ? c->mfield : nullptr, pal ? c->cell_pal : nullptr,
-                                split ? c->shade_list : nullptr, split ? (int)(c->split_frames++ & 1u) : 0,
-                                side ? c->ev_fork : nullptr, dc_merged ? c->dboxes : nullptr, dc_merged ? c->dclr : nullptr,
-                                cr0, ncr));
+    HIPCHK(c, launch_shade_cmin(a, c->sd, st));
   } else {
-    HIPCHK(c, launch_shade(c->dist, c->color_in, c->emissive, c->shade, c->sd, c->reflectivity, st));
-    if (proofs) HIPCHK(c, launch_dist_cmin(c->dist, c->sd.pitch, c->cmin, c->W, c->H, st, mps ? c->hitc : nullptr));
+    HIPCHK(c, launch_shade(a, c->sd, st));
+    if (proofs) HIPCHK(c, launch_dist_cmin(a, c->sd, st));
   }
   if (mps && side) {
     HIPCHK(c, hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
@@ -308,12 +335,27 @@ static int blur_and_merge(rc2dgi_ctx *c, const FramePlan &plan, float4 *&finalGI
   hipStream_t st = c->stream;
   const bool T = c->timing;
   bool merged = false;
+  BlurArgs b;  // (filled once; the launches below differ in their rows, gi_in follows finalGI)
+  b.gi_in = finalGI;
+  b.blur_out = c->blur;
+  b.gi_out = c->gi_spare;
+  b.radius = c->blur_radius;
+  b.color_in = c->color_in;
+  b.temp = c->temp;
+  b.color_out = c->color_out;
+  b.m0 = c->ow0;
+  b.m1 = c->ow1;
+  auto rows = [&b](const std::pair<int, int> &r) -> const BlurArgs & {
+    b.row0 = r.first;
+    b.row1 = r.second;
+    return b;
+  };
   if (c->blur_radius > 0.0f) {
     bool fused = false;
     BlurTaps bt;
     const bool mrg = c->sd.W == c->CW && c->sd.H == c->CH && !c->linux_merge;
     // The fused kernels skip LINEAR taps of weight 0, an identity but for non-finite or huge neighbours
-    // (absmax4, rc2dgi_kernels.hip): they report such a value through odd_flag, and the frame is then redone tap by tap
+    // (absmax4, rc2dgi_blur.hip): they report such a value through odd_flag, and the frame is then redone tap by tap
     // on the device (launch_blur_exact below; one launch that returns at once otherwise).  Whole frames only: a
     // row-strip shard stages its own rows, so it neither sees every value nor holds every row the redo reads.
     unsigned *flag = nullptr;
@@ -326,16 +368,17 @@ static int blur_and_merge(rc2dgi_ctx *c, const FramePlan &plan, float4 *&finalGI
       if (++c->odd_epoch == 0) c->odd_epoch = 1;  // (0: the cleared flag)
       flag = c->odd_flag;
     }
-    const unsigned epoch = c->odd_epoch;
+    b.flag = flag;
+    b.epoch = c->odd_epoch;
     // a fused kernel writes the copied-back GI into gi_spare, which then becomes finalGI: only when
     // every launch of it ran (a refused launch -- shapes it does not take -- falls back before any
     // launch ran, since the shapes are the same for every row interval)
     if (c->blur_path == 0 && blur_rows_plan(c->cd, c->blur_radius, &bt) >= 0) {
       bool ok = true;
-      for (auto &r : plan.blur.iv)
-        ok = ok && launch_blur_rows(finalGI, c->blur, c->gi_spare, c->cd, c->blur_radius, c->color_in, c->temp,
-                                    c->color_out, c->sd, mrg, st, r.first, r.second, c->ow0, c->ow1,
-                                    c->gband ? c->gb0[0] : 0, c->gband ? c->gbn[0] : 0, flag, epoch);
+      b.merge = mrg;
+      b.g0 = c->gband ? c->gb0[0] : 0;
+      b.gn = c->gband ? c->gbn[0] : 0;
+      for (auto &r : plan.blur.iv) ok = ok && launch_blur_rows(rows(r), c->sd, c->cd, st);
       if (!ok && plan.blur.iv.size() > 1) return fail(c, RC2DGI_E_HIP, "fixed-tap blur refused a row interval");
       fused = ok;
       merged = ok && mrg;
@@ -345,28 +388,24 @@ static int blur_and_merge(rc2dgi_ctx *c, const FramePlan &plan, float4 *&finalGI
     if (c->gwin && !merged) return fail(c, RC2DGI_E_STATE, "strip-sized blur textures without the fused blur + merge");
     if (!fused && c->blur_path <= 1 && blur_fused_ok(c->cd, c->blur_radius)) {
       bool ok = true;
-      for (auto &r : plan.blur.iv)
-        ok = ok && launch_blur_fused(finalGI, c->blur, c->gi_spare, c->cd, c->blur_radius, st, r.first, r.second,
-                                     flag, epoch);
+      for (auto &r : plan.blur.iv) ok = ok && launch_blur_fused(rows(r), c->cd, st);
       if (!ok && plan.blur.iv.size() > 1) return fail(c, RC2DGI_E_HIP, "LDS-tiled blur refused a row interval");
       fused = ok;
     }
     if (fused) {
       HIPCHK(c, hipGetLastError());
-      if (flag)
-        HIPCHK(c, launch_blur_exact(flag, epoch, finalGI, c->blur, c->gi_spare, c->cd, c->blur_radius, c->color_in,
-                                    c->temp, c->color_out, c->sd, merged, st));
+      b.merge = merged;
+      if (flag) HIPCHK(c, launch_blur_exact(b, c->sd, c->cd, st));
       if (!c->gwin) std::swap(finalGI, c->gi_spare);  // (gwin: the final GI stays in the strip-sized gi_spare)
     } else {
-      for (auto &r : plan.blur.iv) HIPCHK(c, launch_blur(finalGI, c->blur, c->cd, c->blur_radius, st, r.first, r.second));
+      for (auto &r : plan.blur.iv) HIPCHK(c, launch_blur(rows(r), c->cd, st));
       for (auto &r : plan.blur.iv) HIPCHK(c, launch_blur_copyback(c->blur, finalGI, c->cd, st, r.first, r.second));
     }
   }
   if (T) HIPCHK(c, hipEventRecord(c->ev[4], st));
+  b.gi_in = finalGI;
   if (!merged)
-    for (auto &r : plan.merge.iv)
-      HIPCHK(c, launch_merge(c->color_in, finalGI, c->temp, c->color_out, c->sd, c->cd, st, r.first, r.second,
-                             c->linux_merge, c->ow0));
+    for (auto &r : plan.merge.iv) HIPCHK(c, launch_merge(rows(r), c->sd, c->cd, st, c->linux_merge));
   if (T) HIPCHK(c, hipEventRecord(c->ev[5], st));
   return RC2DGI_OK;
 }

@@ -1,4 +1,27 @@
-// rc2dgi_kernels.h -- host-side launchers for the DoRC2DGI() pass kernels (gfx950).
+// rc2dgi_kernels.h -- host-side launchers for the DoRC2DGI() pass kernels (gfx950), one banner per unit.
+//
+// Pass  <-  reference
+//   k_occupancy     shaders/ScreenUV.fs:10-28          (RC2DGI.cs:278-285), as a 1-bit mask
+//   k_jfa_step      shaders/JumpFlood.fs:11-38         (RC2DGI.cs:296-326)
+//                   + shaders/DistanceField.fs:12-34 fused into the last step (RC2DGI.cs:328-340)
+//   k_rc_level      shaders/RadianceCascades.fs:30-161 (RC2DGI.cs:342-362, 408-433)
+//   k_blur          shaders/Blur.fs:11-37              (RC2DGI.cs:367-379)
+//   k_blur_copyback default shader, blended            (RC2DGI.cs:381-386)
+//   k_merge         shaders/merge.fs:10-15 + copy-back (RC2DGI.cs:389-404)
+//
+// Storage in HBM (pitch-linear, GL row order, row 0 = bottom):
+//   colorRT/emissiveRT/tempRT/colorRT_out  float4  (the reference's RGBA, f32 mode)
+//   jumpRT1/2                              uint32  packed seed texel (sj<<16 | si); the reference's
+//                                                  (u, v) = ((si+0.5)/W, (sj+0.5)/H), B=0, A=1
+//   ScreenUV seeds (J0)                    1 bit   occupancy mask read by the first JFA step
+//   distRT                                 uint16  q = packUNorm16(d) (DistanceField.fs:12-19);
+//                                                  RadianceCascades.fs:30-33 reads q / 65535
+//   giRT1/2, cascadeBlurRT                 float4 (f16 mode: giRT1/2 as RGBA16F)
+// RGBA8 mode (RC2DGI_STORAGE_RGBA8_COMPAT, every render texture RGBA8 as in the literal app):
+//   jumpRT1/2 hold the unorm8 seed uv (kv<<16 | ku), giRT1/2 and cascadeBlurRT are RGBA8 bytes,
+//   the float4 textures hold exactly k * (1/255); stores blend and LINEAR filters in 8 bits.
+// The floating-point arithmetic follows the shader expressions operation by operation
+// (compiled with -ffp-contract=off), so results are reproducible against the CPU oracle.
 #pragma once
 
 #include <cstdint>
@@ -15,19 +38,6 @@ struct ScreenDims {
   int u8;          // RGBA8 render textures (RC2DGI_STORAGE_RGBA8_COMPAT): seeds are unorm8 (u, v)
 };
 
-// fixed bilinear taps of Blur.fs for a dyadic radius (see k_blur_rows)
-struct BlurTaps {
-  int a0;         // column / row offset of the "-radius" tap pair
-  float w0, w2;   // weights of the "-radius" and "+radius" tap pairs
-};
-
-// power-of-two JFA: integer tap offsets and the distance-key scaling (see k_jfa_p2)
-struct JfaTaps {
-  int dx[3], dy[3];
-  float scx, scy, dinit;  // key scale per axis (max(W,H) / W, / H) and the initial minimum max(W,H)^2
-  float inv_mx;           // 1 / max(W,H): distance = sqrt(key) / max(W,H)
-};
-
 struct CascadeDims {
   int CW, CH;
   int pitch;
@@ -37,17 +47,29 @@ struct CascadeDims {
                // cascadeBlurRT as bytes, 8-bit blends and filtering
 };
 
+// ================================================================ rc2dgi_jfa.hip: ScreenUV, JumpFlood, DistanceField
 // ScreenUV (shaders/ScreenUV.fs) as a 1-bit occupancy mask (row pitch mpitch 32-bit words), rows [row0, row1)
 hipError_t launch_occupancy(const float4 *color, unsigned *mask, int mpitch, ScreenDims s, hipStream_t st,
                             int row0 = 0, int row1 = -1);
 // the ScreenUV seed texture J0 (packed seeds) from the mask
 hipError_t launch_seeds_from_mask(const unsigned *mask, int mpitch, unsigned *seeds, ScreenDims s, hipStream_t st);
 
+// power-of-two JFA: integer tap offsets and the distance-key scaling (see k_jfa_p2)
+struct JfaTaps {
+  int dx[3], dy[3];
+  float scx, scy, dinit;  // key scale per axis (max(W,H) / W, / H) and the initial minimum max(W,H)^2
+  float inv_mx;           // 1 / max(W,H): distance = sqrt(key) / max(W,H)
+};
+// integer taps of the power-of-two JFA kernel (false: the float path runs); also used by the
+// row-strip planner
+bool jfa_p2_taps(ScreenDims s, const float off_x[3], const float off_y[3], JfaTaps *tp);
+// the texcoords (i + 0.5) / W of the W columns, then (j + 0.5) / H of the H rows, as the kernels divide (host)
+void tc_table(int W, int H, float *out);
+// x * (1/n) plus one fused correction equals the IEEE quotient (i + 0.5) / n for every i < n (host, exhaustive)
+bool tc_rcp_exact(int n);
+
 // one JumpFlood step (shaders/JumpFlood.fs) over packed seeds (sj<<16 | si, 0x80008000 = none;
 // with s.u8 the stored unorm8 seed uv, kv<<16 | ku, none when ku or kv is 0).
-// first: src is the occupancy mask (pitch in words), else packed seeds (pitch in texels).
-// off_x/off_y = vec2(k,k)*_Aspect.yx*_StepSize for k = -1,0,1 (host-computed).
-// dist != nullptr fuses DistanceField.fs: stores the 16-bit q of packUNorm16.
 // Row-strip shards (window != nullptr, not the first step): tap y (dy = -1, 0, +1) reads its rows
 // from window->base[y], whose local row 0 is global row window->row0[y] (rows taken modulo H: a
 // shard's halo / block buffers, filled by the exchange); the output row j goes to dst row
@@ -57,66 +79,39 @@ struct JfaSrc {
   int row0[3];
   int on;
 };
-hipError_t launch_jfa_step(bool first, const unsigned *src, int src_pitch, unsigned *dst, unsigned short *dist,
-                           ScreenDims s, const float off_x[3], const float off_y[3], hipStream_t st, int row0 = 0,
-                           int row1 = -1,  // output rows [row0, row1) (-1 = H)
-                           const JfaSrc *window = nullptr, int dst_row0 = 0,
-                           int lds = 0,   // LDS-staged taps for short power-of-two steps (tuning jfa_lds)
-                           int small_rt = 1,   // rows per lane of the float-path steps on small screens (tuning jfa_rt)
-                           int jrows = 0,
-                           const float *tc = nullptr,  // float path: the W + H texcoord table (tc_table), or nullptr
-                           int tmode = 0);  // float path texcoords: 0 divide, 1 the table, 2 tc_rcp (tc_rcp_exact)
-// Several device-to-device copies of one device in one launch (the in-process shard exchanges of rc2dgi_do_group:
-// a copy each is a blit launch, and a frame of 8 shards made about 420 of them): pieces whose addresses and sizes
-// are multiples of 16 bytes (copy_piece_ok), at most kCopyBatchMax per launch.
-struct CopyPiece {
-  const void *src;
-  void *dst;
-  size_t bytes;
+struct JfaStepArgs {
+  bool first = false;  // src is the occupancy mask (pitch in words), else packed seeds (pitch in texels)
+  const unsigned *src = nullptr;
+  int src_pitch = 0;
+  unsigned *dst = nullptr;
+  unsigned short *dist = nullptr;  // != nullptr fuses DistanceField.fs: stores the 16-bit q of packUNorm16
+  const float *off_x = nullptr, *off_y = nullptr;  // 3 each: vec2(k,k)*_Aspect.yx*_StepSize for k = -1,0,1 (host)
+  int row0 = 0, row1 = -1;  // output rows [row0, row1) (-1 = H)
+  const JfaSrc *window = nullptr;
+  int dst_row0 = 0;
+  int lds = 0;       // LDS-staged taps for short power-of-two steps (tuning jfa_lds)
+  int small_rt = 1;  // rows per lane of the float-path steps on small screens (tuning jfa_rt)
+  int jrows = 0;     // short isotropic power-of-two steps (S = 1, 2, 4): 4 / 8 consecutive rows per lane, each tap
+                     // row loaded once (tuning jfa_rows; 0: off)
+  const float *tc = nullptr;  // float path: the W + H texcoord table (tc_table), or nullptr
+  int tmode = 0;     // float path texcoords: 0 divide, 1 the table, 2 tc_rcp (tc_rcp_exact)
 };
-constexpr int kCopyBatchMax = 32;
-struct CopyBatch {
-  CopyPiece p[kCopyBatchMax];
-  int n = 0;
-};
-inline bool copy_piece_ok(const void *src, const void *dst, size_t bytes) {
-  return ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | bytes) & 15u) == 0;
-}
-hipError_t launch_copy_batch(const CopyBatch &b, hipStream_t st);
-// the texcoords (i + 0.5) / W of the W columns, then (j + 0.5) / H of the H rows, as the kernels divide (host)
-void tc_table(int W, int H, float *out);
-// x * (1/n) plus one fused correction equals the IEEE quotient (i + 0.5) / n for every i < n (host, exhaustive)
-bool tc_rcp_exact(int n);     // short isotropic power-of-two steps (S = 1, 2, 4): JR = 4 / 8
-                                               // consecutive rows per lane, each tap row loaded once (jfa_rows)
-// integer taps of the power-of-two JFA kernel (false: the float path runs); also used by the
-// row-strip planner
-bool jfa_p2_taps(ScreenDims s, const float off_x[3], const float off_y[3], JfaTaps *tp);
+hipError_t launch_jfa_step(const JfaStepArgs &a, ScreenDims s, hipStream_t st);
 
 // the first four steps in one kernel (k_jfa_coset): 4 where they apply (square power-of-two screens of
 // 512 texels or more), else 0.  launch_jfa_coset reads the ScreenUV mask and writes J_3.
 // (lat 16: steps 0-3 in one kernel; lat 32: steps 0-4)
 int jfa_coset_steps(ScreenDims s, int S, int lat = 16);
+hipError_t launch_jfa_coset(const unsigned *mask, int mpitch, unsigned *dst, ScreenDims s, hipStream_t st,
+                            int lat = 16);
 // the last nt (2..4) JumpFlood steps in one kernel (k_jfa_tail): square power-of-two screens up to 16384 whose last
 // steps tap +-2^(nt-1) .. +-1 texels.  Reads J_{S-nt-1} from src (which must be neither output), writes J_{S-1} to
 // dst, J_{S-2} to dst_prev and the DistanceField.
 bool jfa_tail_ok(ScreenDims s, int S, int nt);
 hipError_t launch_jfa_tail(const unsigned *src, unsigned *dst, unsigned *dst_prev, unsigned short *dist, ScreenDims s,
                            int S, int nt, hipStream_t st);
-hipError_t launch_jfa_coset(const unsigned *mask, int mpitch, unsigned *dst, ScreenDims s, hipStream_t st,
-                            int lat = 16);
 
-// device copies of the host-built workgroup maps of k_rc_level, one per launch geometry
-struct RcMapCache {
-  struct Entry {
-    int nwg, tiles_x, tiles_y, ngrp, code, tile_w, tile_h;
-    uint2 *dev;
-  };
-  std::vector<Entry> entries;
-  void clear();
-  void retain(const std::vector<int> &codes);  // free the maps of every other order code
-  ~RcMapCache();
-};
-
+// ================================================================ rc2dgi_side.hip: what the march reads besides distRT
 // coarse lower bound of the distance field: kCminDim x kCminDim cells of 2^dist_cmin_shift texels
 // (row-major, kCminDim per row): 64 x 64 byte entries (4 KB of LDS per workgroup, as the round-2
 // 32 x 32 float table, which the finer cells beat: RC 1.717 -> 1.707 ms on one box, and which the
@@ -131,6 +126,87 @@ constexpr float kCminScale = RC2DGI_CMIN_SCALE, kCminStep = 1.0f / RC2DGI_CMIN_S
 __host__ __device__ __forceinline__ float cmin_value(CminT v) {
   return (float)v * kCminStep;  // exact: k < 2^8, power-of-two step
 }
+int dist_cmin_shift(int W, int H);
+// Surface palettes (launch_shade_cmin with mf / cpal): kCellPal distinct hit records per bound-table cell, and
+// the march field mf = distRT with each hittable texel's q (<= 65: decode_dist < 0.001) replaced by the index of
+// its record in its cell's palette, kCellPal when the palette is full (the record is then read from shade).
+// A march reading mf takes the same samples (a hit is still a value <= 65, other texels keep q) and finds a
+// hit's record in a 1 MB table shared by all the rays that end on one surface of the cell.
+constexpr int kCellPal = 15, kCellPalStride = 16;  // entries per cell (index 15 marks "no entry"), slots per cell
+// Directional clear distances of the march proofs (k_rc_level, one-probe tiles): kDirBins angular bins x
+// kCminDim^2 cells, bytes (k_dir_clear)
+constexpr int kDirBins = 64;
+// What the record and bound-table launchers take; launch_shade and launch_dist_cmin read the first seven fields.
+struct ShadeCminArgs {
+  const unsigned short *dist = nullptr;
+  const float4 *color = nullptr, *emis = nullptr;
+  float4 *shade = nullptr;  // (launch_shade_cmin: nullptr with mf / cpal and cell rows: no record texture)
+  float reflectivity = 0.0f;
+  CminT *cmin = nullptr;
+  // hitc (optional): per cell 1 when a texel the march may sample there passes the hit test (the REPEAT wrap of
+  // u = 1 / v = 1 onto column / row 0 included in the last cell column / row), else 0
+  unsigned char *hitc = nullptr;
+  unsigned short *mf = nullptr;  // the march field and the palettes (above), or nullptr
+  float4 *cpal = nullptr;
+  // list (optional, with mf / cpal; shade_split_ok sizes): 2 + kCminDim^2 words, zeroed once; the pass then runs
+  // split (k_shade_scan over every cell, k_shade_cells over the cells holding a hittable texel).  `parity` must
+  // alternate from one split pass to the next (k_shade_cells clears the other parity's counter).
+  unsigned *list = nullptr;
+  int parity = 0;
+  hipEvent_t after_scan = nullptr;  // (split: recorded after the scan)
+  const int4 *boxes = nullptr;      // (split: k_dir_clear merged into the launch, with dclr)
+  unsigned char *dclr = nullptr;
+  int cr0 = 0, ncr = kCminDim;      // cell rows [cr0, cr0 + ncr) only (with mf / cpal)
+};
+// surface records for the RC march's hits (k_shade): (emission, 1) or (albedo, reflectivity) at
+// every texel whose distance passes the march's hit test; other texels untouched
+hipError_t launch_shade(const ShadeCminArgs &a, ScreenDims s, hipStream_t st);
+hipError_t launch_dist_cmin(const ShadeCminArgs &a, ScreenDims s, hipStream_t st);
+// launch_shade and launch_dist_cmin (with hitc) as one pass over distRT: square power-of-two screens with
+// cells of >= 64 texels only (shade_cmin_fused_ok; 4096^2 and up)
+bool shade_cmin_fused_ok(int W, int H, int pitch);
+bool shade_split_ok(int W, int H);
+hipError_t launch_shade_cmin(const ShadeCminArgs &a, ScreenDims s, hipStream_t st);
+// per bin and step of k_dir_clear: the box of cells (x0, x1, y0, y1 relative to the start cell) the step's
+// points reach, for cells of 2^csh texels; kDirBins x kCminDim entries (host)
+void dir_clear_boxes(int csh, int4 *boxes);
+hipError_t launch_dir_clear(const unsigned char *hitc, const int4 *boxes, unsigned char *dclr, hipStream_t st);
+
+// distRT -> 8x8-tiled copy (tiles row-major, ceil(W/8) tiles per row; rows padded to 8)
+hipError_t launch_dist_tile(const unsigned short *dist, int pitch, unsigned short *tiled, int W, int H,
+                            hipStream_t st);
+// distRT -> packed 14-texel packets (16 B each: the minimum q + one excess byte per texel)
+size_t dist_packed_bytes(int W, int H);
+hipError_t launch_dist_pack(const unsigned short *dist, int pitch, uint4 *packed, int W, int H, hipStream_t st);
+// distRT -> nibble-predicted 26-texel packets (base, slope, one 4-bit residual per texel)
+size_t dist_nib_bytes(int W, int H);
+hipError_t launch_dist_nib(const unsigned short *dist, int pitch, uint4 *packed, int W, int H, hipStream_t st);
+
+// ================================================================ rc2dgi_rc_launch.hip: the cascade levels' host glue
+// device copies of the host-built workgroup maps of k_rc_level, one per launch geometry
+struct RcMapCache {
+  struct Entry {
+    int nwg, tiles_x, tiles_y, ngrp, code, tile_w, tile_h;
+    uint2 *dev;
+  };
+  std::vector<Entry> entries;
+  void clear();
+  void retain(const std::vector<int> &codes);  // free the maps of every other order code
+  ~RcMapCache();
+};
+// rc_order code (px | py << 8 | dg << 16 | oriented << 24 | banded << 25): logical workgroups
+// 0..n-1 -> (tile, direction group), tiles of tile_w x tile_h probes
+int rc_order_plan(int code, int tiles_x, int tiles_y, int tile_w, int tile_h, int ngrp, int *tiles, int *groups,
+                  int n);
+int rc_wg_map_plan(int code, int tiles_x, int tiles_y, int tile_w, int tile_h, int ngrp, int *tiles, int *groups,
+                  int n);
+
+int rc_variant_count();
+const char *rc_variant_name(int v);
+bool rc_variant_tiled(int v);  // reads the 8x8-tiled distance field
+bool rc_variant_packed(int v);  // reads the packed distance field
+bool rc_variant_nib(int v);     // reads the nibble-predicted distance field
+bool rc_variant_one_probe(int v);  // one probe and one direction block per lane (directional proofs apply)
 
 struct RcLevelArgs {
   const float4 *upper;   // G_{L+1} (nullptr at the top level)
@@ -170,91 +246,6 @@ struct RcLevelArgs {
 // IEEE quotient under div_res mode 2 (host, exhaustive)
 bool rc_div_exact(int n, int level, bool top);
 
-// The cascade chain (rc2dgi_rc_chain.hip, tuning rc_chain): the levels a[0 .. n) (consecutive, downwards; a[0]
-// is the top level, or the level below it with the top already written to a[0].upper) in one launch of 16x16x1
-// tiles (unr: the march unrolled 32 as variant 13, else rolled as variant 0), f32 cascades, whole levels.  Each
-// level's `out` must be a buffer of its own (no level reads what another writes in the same launch).
-// rc_chain_timeouts: workgroups that stopped waiting for their upper tiles since the chain's buffers were made
-// (synchronises the stream; 0 in a correct run).
-struct RcChain;
-RcChain *rc_chain_create();
-void rc_chain_destroy(RcChain *ch);
-bool rc_chain_ok(int nlev);
-// spin: polls per wait before a workgroup gives up (0: the default bound; < 0 diagnostic: every wait times out)
-hipError_t launch_rc_chain(RcChain *ch, const RcLevelArgs *a, int nlev, ScreenDims s, CascadeDims c, int unr,
-                           hipStream_t st, bool tight = false, int spin = 0);
-int rc_chain_timeouts(RcChain *ch, hipStream_t st);
-// a chained frame that completed since the last call had a workgroup stop waiting (its results are wrong): reads
-// and clears the host-mapped error word the kernel sets; no synchronisation (frames still running report later)
-bool rc_chain_take_error(RcChain *ch);
-// the argument block, error word and `nflags` readiness flags (zeroed), made at configuration time
-hipError_t rc_chain_reserve(RcChain *ch, size_t nflags);
-
-int dist_cmin_shift(int W, int H);
-// hitc (optional): per cell 1 when a texel the march may sample there passes the hit test (the REPEAT wrap of
-// u = 1 / v = 1 onto column / row 0 included in the last cell column / row), else 0
-// launch_shade and launch_dist_cmin (with hitc) as one pass over distRT: square power-of-two screens with
-// cells of >= 64 texels only (shade_cmin_fused_ok; 4096^2 and up)
-bool shade_cmin_fused_ok(int W, int H, int pitch);
-// Surface palettes (launch_shade_cmin with mf / cpal): kCellPal distinct hit records per bound-table cell, and
-// the march field mf = distRT with each hittable texel's q (<= 65: decode_dist < 0.001) replaced by the index of
-// its record in its cell's palette, kCellPal when the palette is full (the record is then read from shade).
-// A march reading mf takes the same samples (a hit is still a value <= 65, other texels keep q) and finds a
-// hit's record in a 1 MB table shared by all the rays that end on one surface of the cell.
-constexpr int kCellPal = 15, kCellPalStride = 16;  // entries per cell (index 15 marks "no entry"), slots per cell
-// list (optional, with mf / cpal; shade_split_ok sizes): 2 + kCminDim^2 words, zeroed once; the pass then runs
-// split (k_shade_scan over every cell, k_shade_cells over the cells holding a hittable texel).  `parity` must
-// alternate from one split pass to the next (k_shade_cells clears the other parity's counter).
-bool shade_split_ok(int W, int H);
-hipError_t launch_shade_cmin(const unsigned short *dist, const float4 *color, const float4 *emis, float4 *shade,
-                             ScreenDims s, float reflectivity, CminT *cmin, unsigned char *hitc, hipStream_t st,
-                             unsigned short *mf = nullptr, float4 *cpal = nullptr, unsigned *list = nullptr,
-                             int parity = 0, hipEvent_t after_scan = nullptr,  // (split: recorded after the scan)
-                             const int4 *boxes = nullptr, unsigned char *dclr = nullptr,  // (split: k_dir_clear merged)
-                             int cr0 = 0, int ncr = kCminDim);  // cell rows [cr0, cr0 + ncr) only (with mf / cpal; shade
-                                                                // may then be nullptr: no record texture)
-hipError_t launch_dist_cmin(const unsigned short *dist, int pitch, CminT *cmin, int W, int H, hipStream_t st,
-                            unsigned char *hitc = nullptr);
-// Directional clear distances of the march proofs (k_rc_level, one-probe tiles): kDirBins angular bins x
-// kCminDim^2 cells, bytes (k_dir_clear)
-constexpr int kDirBins = 64;
-// per bin and step of k_dir_clear: the box of cells (x0, x1, y0, y1 relative to the start cell) the step's
-// points reach, for cells of 2^csh texels; kDirBins x kCminDim entries (host)
-void dir_clear_boxes(int csh, int4 *boxes);
-hipError_t launch_dir_clear(const unsigned char *hitc, const int4 *boxes, unsigned char *dclr, hipStream_t st);
-
-// distRT -> 8x8-tiled copy (tiles row-major, ceil(W/8) tiles per row; rows padded to 8)
-hipError_t launch_dist_tile(const unsigned short *dist, int pitch, unsigned short *tiled, int W, int H,
-                            hipStream_t st);
-
-// rc_order code (px | py << 8 | dg << 16 | oriented << 24 | banded << 25): logical workgroups
-// 0..n-1 -> (tile, direction group), tiles of tile_w x tile_h probes
-int rc_order_plan(int code, int tiles_x, int tiles_y, int tile_w, int tile_h, int ngrp, int *tiles, int *groups,
-                  int n);
-int rc_wg_map_plan(int code, int tiles_x, int tiles_y, int tile_w, int tile_h, int ngrp, int *tiles, int *groups,
-                  int n);
-
-int rc_variant_count();
-const char *rc_variant_name(int v);
-bool rc_variant_tiled(int v);  // reads the 8x8-tiled distance field
-bool rc_variant_packed(int v);  // reads the packed distance field
-bool rc_variant_nib(int v);     // reads the nibble-predicted distance field
-bool rc_variant_one_probe(int v);  // one probe and one direction block per lane (directional proofs apply)
-
-// distRT -> packed 14-texel packets (16 B each: the minimum q + one excess byte per texel)
-size_t dist_packed_bytes(int W, int H);
-hipError_t launch_dist_pack(const unsigned short *dist, int pitch, uint4 *packed, int W, int H, hipStream_t st);
-// distRT -> nibble-predicted 26-texel packets (base, slope, one 4-bit residual per texel)
-size_t dist_nib_bytes(int W, int H);
-hipError_t launch_dist_nib(const unsigned short *dist, int pitch, uint4 *packed, int W, int H, hipStream_t st);
-
-
-// surface records for the RC march's hits (k_shade): (emission, 1) or (albedo, reflectivity) at
-// every texel whose distance passes the march's hit test; other texels untouched
-hipError_t launch_shade(const unsigned short *dist, const float4 *color, const float4 *emis, float4 *shade,
-                        ScreenDims s, float reflectivity, hipStream_t st);
-
-// CalculateRayRange's end of level L (RadianceCascades.fs:38-46), as k_rc_level computes it
 // _Aspect (RC2DGI.cs:273): screen size over its larger side
 inline void rc_aspect(int W, int H, float &aspx, float &aspy) {
   const int mx = W > H ? W : H;
@@ -279,6 +270,7 @@ inline void rc_exit_terms(float dx, float dy, float aspx, float aspy, float out[
   }
 }
 
+// CalculateRayRange's end of level L (RadianceCascades.fs:38-46), as k_rc_level computes it
 inline float rc_ray_end(int level, int N, float ray_range) {
   return ((float)((1 << (level * 2 + 2)) - 1) / (float)((1 << (N * 2)) - 1)) * ray_range;
 }
@@ -295,47 +287,95 @@ hipError_t launch_rc_block_const(bool top, const float4 *src, float4 *dst, int l
 hipError_t launch_rc_fill(float4 *out, const float4 *cst, CascadeDims c, int level, hipStream_t st, int p0 = 0,
                           int p1 = -1, int b0 = 0, int bn = 0);  // (rows [p0, p1) of every block; bn > 0: banded)
 
+// ================================================================ rc2dgi_rc_chain.hip: the cascade chain
+// The cascade chain (tuning rc_chain): the levels a[0 .. n) (consecutive, downwards; a[0] is the top level, or the level below it with the top already written to a[0].upper) in one launch of 16x16x1
+// tiles (unr: the march unrolled 32 as variant 13, else rolled as variant 0), f32 cascades, whole levels.  Each
+// level's `out` must be a buffer of its own (no level reads what another writes in the same launch).
+// rc_chain_timeouts: workgroups that stopped waiting for their upper tiles since the chain's buffers were made
+// (synchronises the stream; 0 in a correct run).
+struct RcChain;
+RcChain *rc_chain_create();
+void rc_chain_destroy(RcChain *ch);
+bool rc_chain_ok(int nlev);
+// spin: polls per wait before a workgroup gives up (0: the default bound; < 0 diagnostic: every wait times out)
+hipError_t launch_rc_chain(RcChain *ch, const RcLevelArgs *a, int nlev, ScreenDims s, CascadeDims c, int unr,
+                           hipStream_t st, bool tight = false, int spin = 0);
+int rc_chain_timeouts(RcChain *ch, hipStream_t st);
+// a chained frame that completed since the last call had a workgroup stop waiting (its results are wrong): reads
+// and clears the host-mapped error word the kernel sets; no synchronisation (frames still running report later)
+bool rc_chain_take_error(RcChain *ch);
+// the argument block, error word and `nflags` readiness flags (zeroed), made at configuration time
+hipError_t rc_chain_reserve(RcChain *ch, size_t nflags);
+
+// ================================================================ rc2dgi_blur.hip: blur, copy-back, merge
+// fixed bilinear taps of Blur.fs for a dyadic radius (see k_blur_rows)
+struct BlurTaps {
+  int a0;         // column / row offset of the "-radius" tap pair
+  float w0, w2;   // weights of the "-radius" and "+radius" tap pairs
+};
+// What the blur and merge launchers take; each reads the fields its pass has.
+struct BlurArgs {
+  const float4 *gi_in = nullptr;  // G_0 (the merge: the blurred, copied-back GI)
+  float4 *blur_out = nullptr;     // cascadeBlurRT
+  float4 *gi_out = nullptr;       // the copied-back GI of the fused kernels; may not alias gi_in
+  float radius = 0.0f;
+  const float4 *color_in = nullptr;  // the merge: colorRT in, tempRT and colorRT out
+  float4 *temp = nullptr, *color_out = nullptr;
+  bool merge = false;             // the fused kernels run merge.fs and its copy-back too (screen == cascade size)
+  // flag: set to `epoch` when a value met breaks the identities the fused kernels rest on -- see absmax4 in
+  // rc2dgi_blur.hip; nullptr: not reported
+  unsigned *flag = nullptr;
+  unsigned epoch = 0;
+  int row0 = 0, row1 = -1;  // rows [row0, row1) of the pass (-1: all)
+  // merge outputs: temp / color_out hold screen rows [m0, m1) from their row 0 -- a row-strip shard's own rows; m1 = -1:
+  // every row -- and (launch_blur_rows) one guard row after those, which receives the merge of every row outside them
+  int m0 = 0, m1 = -1;
+  int g0 = 0, gn = 0;  // launch_blur_rows: gi_in holds the gn cascade rows from g0 on, cyclically -- a shard's banded
+                       // level 0; gn <= 0: every row
+};
 // Blur.fs into blur_out, then the default-shader blended copy-back into gi (RC2DGI.cs:367-387)
-hipError_t launch_blur(const float4 *gi, float4 *blur_out, CascadeDims c, float radius, hipStream_t st,
-                       int row0 = 0, int row1 = -1);
+hipError_t launch_blur(const BlurArgs &a, CascadeDims c, hipStream_t st);
 hipError_t launch_blur_copyback(const float4 *blur, float4 *gi, CascadeDims c, hipStream_t st, int row0 = 0,
                                 int row1 = -1);
-// both in one pass (power-of-two cascade sizes, radius <= 6); gi_out may not alias gi_in.
-// Returns false (nothing launched) when the shape is not supported.
-bool blur_fused_ok(CascadeDims c, float radius);  // power-of-two sizes, radius <= 6
-// (flag: set to `epoch` when a value met breaks the identities the fused kernels rest on -- see absmax4 in
-// rc2dgi_kernels.hip; nullptr: not reported)
-bool launch_blur_fused(const float4 *gi_in, float4 *blur_out, float4 *gi_out, CascadeDims c, float radius,
-                       hipStream_t st, int row0 = 0, int row1 = -1, unsigned *flag = nullptr, unsigned epoch = 0);
-// what launch_blur + launch_blur_copyback (+ launch_merge when `merge`) leave, from gi_in alone into blur_out / gi_out
-// (/ temp / color_out), on the device's say: the kernel returns at once unless *flag == epoch.  Whole frames of
-// power-of-two cascades; gi_out may not alias gi_in.
-hipError_t launch_blur_exact(const unsigned *flag, unsigned epoch, const float4 *gi_in, float4 *blur_out, float4 *gi_out,
-                             CascadeDims c, float radius, const float4 *color_in, float4 *temp, float4 *color_out,
-                             ScreenDims s, bool merge, hipStream_t st);
-
-// Blur + copy-back (+ merge and its copy-back when `merge`) with fixed taps; false when the
+// both in one pass (power-of-two cascade sizes, radius <= 6).  Returns false (nothing launched) when the shape is
+// not supported.
+bool blur_fused_ok(CascadeDims c, float radius);
+bool launch_blur_fused(const BlurArgs &a, CascadeDims c, hipStream_t st);
+// Blur + copy-back (+ merge and its copy-back when a.merge) with fixed taps; false when the
 // radius / sizes do not allow it (see k_blur_rows).  blur_rows_plan: F = floor(radius) or -1.
 int blur_rows_plan(CascadeDims c, float radius, BlurTaps *bt);
-// (merge outputs: temp / color_out hold screen rows [m0, m1) from their row 0 -- a row-strip shard's own rows; m1 = -1:
-// every row -- and one guard row after those, which receives the merge of every row outside them; gi_in holds the
-// gn cascade rows from g0 on, cyclically -- a shard's banded level 0; gn <= 0: every row)
-bool launch_blur_rows(const float4 *gi_in, float4 *blur_out, float4 *gi_out, CascadeDims c, float radius,
-                      const float4 *color_in, float4 *temp, float4 *color_out, ScreenDims s, bool merge,
-                      hipStream_t st, int row0 = 0, int row1 = -1, int m0 = 0, int m1 = -1, int g0 = 0, int gn = 0,
-                      unsigned *flag = nullptr, unsigned epoch = 0);
-
+bool launch_blur_rows(const BlurArgs &a, ScreenDims s, CascadeDims c, hipStream_t st);
+// what launch_blur + launch_blur_copyback (+ launch_merge when a.merge) leave, from gi_in alone into blur_out / gi_out
+// (/ temp / color_out), on the device's say: the kernel returns at once unless *flag == epoch.  Whole frames of
+// power-of-two cascades.
+hipError_t launch_blur_exact(const BlurArgs &a, ScreenDims s, CascadeDims c, hipStream_t st);
 // merge.fs into temp, then tempRT -> colorRT copy-back (RC2DGI.cs:389-404); linux_merge: raylib's default
 // shader in place of merge.fs (RC2DGI_FLAG_LINUX_MERGE_FALLBACK)
-// (temp / color_out hold screen row m0 as their row 0)
-hipError_t launch_merge(const float4 *color_in, const float4 *gi, float4 *temp, float4 *color_out, ScreenDims s,
-                        CascadeDims c, hipStream_t st, int row0 = 0, int row1 = -1, bool linux_merge = false, int m0 = 0);
+hipError_t launch_merge(const BlurArgs &a, ScreenDims s, CascadeDims c, hipStream_t st, bool linux_merge = false);
 
+// ================================================================ rc2dgi_copy.hip: conversions, batched copies
 // format conversion for uploads from device memory: RGBA8 unorm -> float4 (k/255; u8: k*(1/255),
 // the value an RGBA8 texture fetch returns)
 hipError_t launch_unorm8_to_f32(const unsigned char *src, int src_pitch_bytes, float4 *dst, int dst_pitch, int W,
                                 int H, hipStream_t st, bool u8 = false);
 // a float upload into an RGBA8 texture: v -> rint(clamp(v) * 255) * (1/255), in place
 hipError_t launch_quantize_u8(float4 *buf, int pitch, int W, int H, hipStream_t st);
+// Several device-to-device copies of one device in one launch (the in-process shard exchanges of rc2dgi_do_group:
+// a copy each is a blit launch, and a frame of 8 shards made about 420 of them): pieces whose addresses and sizes
+// are multiples of 16 bytes (copy_piece_ok), at most kCopyBatchMax per launch.
+struct CopyPiece {
+  const void *src;
+  void *dst;
+  size_t bytes;
+};
+constexpr int kCopyBatchMax = 32;
+struct CopyBatch {
+  CopyPiece p[kCopyBatchMax];
+  int n = 0;
+};
+inline bool copy_piece_ok(const void *src, const void *dst, size_t bytes) {
+  return ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | bytes) & 15u) == 0;
+}
+hipError_t launch_copy_batch(const CopyBatch &b, hipStream_t st);
 
 }  // namespace rc2dgi

@@ -1,18 +1,18 @@
 // rc2dgi_rc.h -- the RadianceCascades.fs level kernel (k_rc_level) and its launch template,
 // shared by the translation units that instantiate its tile variants (rc2dgi_rc_*.hip, built in
-// parallel) and by rc2dgi_kernels.hip (decode_dist, the workgroup-order maps).
+// parallel), by rc2dgi_rc_launch.hip (RcParams, the workgroup-order maps) and by rc2dgi_side.hip (decode_dist, the
+// packet formats).
 #pragma once
 
 #include <type_traits>
 
 #include "rc2dgi_device.h"
 #include "rc2dgi_kernels.h"
+#include "rc2dgi_launch.h"
 
 namespace rc2dgi {
 
-static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-// host-built workgroup map of one launch geometry (rc2dgi_kernels.hip)
+// host-built workgroup map of one launch geometry (rc2dgi_rc_launch.hip)
 const uint2 *rc_wg_map(RcMapCache *cache, int nwg, int tiles_x, int tiles_y, int ngrp, int code, int tile_w,
                        int tile_h);
 
@@ -49,7 +49,7 @@ struct RcParams {
 #endif
 };
 
-// the level's parameters that do not depend on the tile shape (rc2dgi_kernels.hip; rc_tile_params adds those)
+// the level's parameters that do not depend on the tile shape (rc2dgi_rc_launch.hip; rc_tile_params adds those)
 RcParams rc_level_params(const RcLevelArgs &a, ScreenDims s, CascadeDims c);
 
 // The cascade chain (k_rc_level<..., CH = true>, launched by rc2dgi_rc_chain.hip): the levels below the top in

@@ -1015,7 +1015,7 @@ def test_miss_proofs_are_bit_identical(RC2DGI, W, H, N, rr, rs, scene, storage):
 
 
 def dir_clear_cpu(hitc, boxes):
-    """k_dir_clear restated (rc2dgi_kernels.hip): per angular bin j and cell (cy, cx) of the 64 x 64 grid, the
+    """k_dir_clear restated (rc2dgi_side.hip): per angular bin j and cell (cy, cx) of the 64 x 64 grid, the
     first step s whose box (boxes[j, s] = x0, x1, y0, y1 cell offsets, clipped to the grid) holds a hit cell,
     if that comes before the first step whose box leaves the grid (vertically: the row's first such step;
     sideways: the cell's), else 255."""

@@ -14,7 +14,7 @@ CSRC = os.path.join(ROOT, "radiancecascade2dglobalillumination_amd", "csrc")
 
 
 def variant_count():
-    src = open(os.path.join(CSRC, "rc2dgi_kernels.hip")).read()
+    src = open(os.path.join(CSRC, "rc2dgi_rc_launch.hip")).read()
     body = src[src.index("kRcVariantNames[] = {"):]
     return len(re.findall(r'"[^"]+"', body[:body.index("};")]))
 
