@@ -1,6 +1,6 @@
 /* layout.c -- sizeof / offsetof of the ABI structs, as the C compiler lays them out, for
  * tests/test_host_cpu.py to compare with the C# StructLayout(Sequential) mirrors in
- * host/csharp/RC2DGINative.cs (Config, Prim; View: tests/test_present_cpu.py). */
+ * host/csharp/RC2DGINative.cs (Config, Prim; View: tests/test_present_cpu.py; Ray, RayHit: tests/test_query_cpu.py). */
 #include <stddef.h>
 #include <stdio.h>
 
@@ -40,5 +40,24 @@ int main(void) {
   F(rc2dgi_view, g);
   F(rc2dgi_view, b);
   F(rc2dgi_view, a);
+  printf("rc2dgi_ray %zu\n", sizeof(rc2dgi_ray));
+  F(rc2dgi_ray, ox);
+  F(rc2dgi_ray, oy);
+  F(rc2dgi_ray, dx);
+  F(rc2dgi_ray, dy);
+  F(rc2dgi_ray, t0);
+  F(rc2dgi_ray, t1);
+  printf("rc2dgi_rayhit %zu\n", sizeof(rc2dgi_rayhit));
+  F(rc2dgi_rayhit, status);
+  F(rc2dgi_rayhit, steps);
+  F(rc2dgi_rayhit, ix);
+  F(rc2dgi_rayhit, iy);
+  F(rc2dgi_rayhit, t);
+  F(rc2dgi_rayhit, u);
+  F(rc2dgi_rayhit, v);
+  F(rc2dgi_rayhit, r);
+  F(rc2dgi_rayhit, g);
+  F(rc2dgi_rayhit, b);
+  F(rc2dgi_rayhit, a);
   return 0;
 }

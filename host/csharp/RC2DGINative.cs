@@ -64,6 +64,32 @@ static unsafe class RC2DGINative
     [DllImport(Lib)] public static extern int rc2dgi_compose(IntPtr ctx, View* views, int n, int outW, int outH, byte* clearRgba, void* host, int pitchBytes);
     [DllImport(Lib)] public static extern int rc2dgi_compose_device(IntPtr ctx, View* views, int n, int outW, int outH, byte* clearRgba, void* dev, int pitchBytes);
 
+    // Queries: a few values of the frame without a Download.  rc2dgi_sample: texture(T, (u, v)) for n points
+    // (uv: 2 floats a point, GL coordinates, v up -- the centre of y-down pixel (x, y) of a W x H texture is
+    // ((x + 0.5f) / W, 1 - (y + 0.5f) / H); rgba: 4 floats a point; filter as View.Filter).  rc2dgi_raycast:
+    // SampleRadianceSDF (RadianceCascades.fs:60-92) for n rays over the last frame.
+    [StructLayout(LayoutKind.Sequential, Size = 24)]
+    public struct Ray
+    {
+        public float Ox, Oy;           // origin, GL texture coordinates
+        public float Dx, Dy;           // direction, used as given
+        public float T0, T1;           // the interval marched
+    }
+    [StructLayout(LayoutKind.Sequential, Size = 44)]
+    public struct RayHit
+    {
+        public int Status;             // RayStatus
+        public int Steps;              // distRT texels read
+        public int Ix, Iy;             // the hit texel (GL order), or (-1, -1)
+        public float T, U, V;          // where the loop ended
+        public float R, G, B, A;       // the shader's hit record
+    }
+    public enum RayStatus { Invalid = -1, Range = 0, Edge = 1, Emissive = 2, Surface = 3, Steps = 4 }
+    [DllImport(Lib)] public static extern int rc2dgi_sample(IntPtr ctx, int which, int filter, float* uv, int n, float* rgba);
+    [DllImport(Lib)] public static extern int rc2dgi_sample_device(IntPtr ctx, int which, int filter, void* uvDev, int n, void* rgbaDev);
+    [DllImport(Lib)] public static extern int rc2dgi_raycast(IntPtr ctx, Ray* rays, int n, RayHit* hits);
+    [DllImport(Lib)] public static extern int rc2dgi_raycast_device(IntPtr ctx, void* raysDev, int n, void* hitsDev);
+
     static IntPtr ctx;
     static Config config;
     static byte[] scratch = Array.Empty<byte>();
@@ -131,6 +157,30 @@ static unsafe class RC2DGINative
             Check(rc2dgi_compose(ctx, views, thumbnails ? n : 1, w, h, null, p, w * 4), "compose");
             Raylib.UpdateTexture(windowTexture, p);
         }
+    }
+
+    // The light arriving at a window position (y down): one LINEAR sample of the final GI instead of a Download.
+    public static System.Numerics.Vector4 LightAt(float x, float y)
+    {
+        float* uv = stackalloc float[2] { x / config.ScreenWidth, 1f - y / config.ScreenHeight };
+        float* c = stackalloc float[4];
+        Check(rc2dgi_sample(ctx, (int)RT.FinalGI, 0, uv, 1, c), "sample");
+        return new System.Numerics.Vector4(c[0], c[1], c[2], c[3]);
+    }
+
+    // Do two window positions see each other?  One ray from a to b over distRT: it ends by range when nothing is hit.
+    public static bool Visible(System.Numerics.Vector2 a, System.Numerics.Vector2 b)
+    {
+        float w = config.ScreenWidth, h = config.ScreenHeight, mx = Math.Max(w, h);
+        // the march evaluates px = ox + t * dx * (h / mx), py = oy + t * dy * (w / mx) and advances t by distRT's
+        // value, a length in texture coordinates: the direction below moves one such unit per unit of t (a longer one
+        // would step through walls), and the ray reaches b at t = len
+        float ux = (b.X - a.X) / w, uy = -(b.Y - a.Y) / h, len = MathF.Sqrt(ux * ux + uy * uy);
+        if (len == 0f) return true;
+        var ray = new Ray { Ox = a.X / w, Oy = 1f - a.Y / h, Dx = ux / len * (mx / h), Dy = uy / len * (mx / w), T0 = 0f, T1 = len };
+        RayHit hit;
+        Check(rc2dgi_raycast(ctx, &ray, 1, &hit), "raycast");
+        return hit.Status == (int)RayStatus.Range;
     }
 
     public static Prim Rect(Rectangle r, Color c) => new Prim { Kind = 0, X = r.X, Y = r.Y, W = r.Width, H = r.Height, R = c.R, G = c.G, B = c.B, A = c.A };

@@ -202,6 +202,82 @@ int rc2dgi_compose(rc2dgi_ctx *ctx, const rc2dgi_view *views, int n, int out_w, 
 int rc2dgi_compose_device(rc2dgi_ctx *ctx, const rc2dgi_view *views, int n, int out_w, int out_h,
                           const unsigned char *clear_rgba, void *dev, int pitch_bytes);
 
+/* ---- queries: a few values of the frame without downloading a texture.  The two reads RadianceCascades.fs makes --
+ * a texture fetch and SampleRadianceSDF -- for a caller's points and rays, one kernel a call.  (The light arriving at a
+ * sprite: a sample of FINAL_GI; the nearest wall: a sample of JUMP2 / DIST; a line of sight, what lies under the
+ * cursor: a ray cast.)
+ *
+ * Point samples: rgba[k] = texture(T, (u, v)[k]) for n points, uv = n x 2 floats, rgba = n x 4 floats.
+ *   which    any rc2dgi_rt, RC2DGI_RT_FINAL_GI included; filter RC2DGI_FILTER_RT / _POINT / _LINEAR as for a view.
+ *   (u, v)   GL texture coordinates, v up, row 0 at the bottom: the coordinates the shaders use.  A host with y-down
+ *            pixels passes ((x + 0.5f) / W, 1 - (y + 0.5f) / H) for the centre of pixel (x, y) of a W x H texture.
+ *   POINT    the texel NEAREST + REPEAT names: per axis of n texels, floor(u * n) & (n - 1) when n is a power of
+ *            two, else min((int)(min(u - floor(u), 0.99999994f) * n), n - 1).
+ *   LINEAR   the four REPEAT-wrapped taps and weights of GL's LINEAR filter (x = u * n - 0.5, or
+ *            (u - floor(u)) * n - 0.5 when n is no power of two; i0 = floor(x), w = x - i0), lerped as the texture's
+ *            storage does: fma(w, b - a, a), x then y, on floats (f32; f16 after the exact unpack), 8.8 fixed point on
+ *            the bytes (rgba8: w8 = rint(w * 256), (a * 256 + (b - a) * w8 + 128) >> 8, the result k * (1/255)).
+ *   Texels   a texel's value is what rc2dgi_download returns for it as floats -- the list under rc2dgi_compose:
+ *            JUMP1 / JUMP2 decoded, DIST its hi / lo bytes, COLOR the input before the first frame and the merged
+ *            output after, GI2 (0, 0, 0, 1) with one cascade.  These are the functions rc2dgi_compose's kernel calls: a
+ *            sample equals what a view would fetch at that texcoord.
+ *   A point with a non-finite u or v yields four quiet NaNs (0x7FC00000) and reads no memory; every finite value,
+ *   however large, addresses a texel of the texture (the index is masked or clamped).  n == 0 is a successful no-op.
+ *
+ * Ray casts: SampleRadianceSDF (RadianceCascades.fs:60-92) for n rays, over the last frame's distRT, the input
+ * colorRT (the painted scene, not the merged output) and emissiveRT as they are now.  With asp = (W, H) / max(W, H)
+ * (_Aspect, RC2DGI.cs:273) and t = t0, each of at most 32 steps evaluates, every operation single and unfused, in
+ * this order,
+ *            px = ox + (t * dx) * asp.y,  py = oy + (t * dy) * asp.x
+ * (the direction as given: it is not normalised) and applies in order:
+ *   1. t > t1: RC2DGI_RAY_RANGE;
+ *   2. else px < 0 || py < 0 || px > 1 || py > 1: RC2DGI_RAY_EDGE;
+ *   3. else read q, the 16-bit distance of texel (ix, iy) = the POINT texel of (px, py) above (so px == 1.0 reads
+ *      column 0, as the shader's REPEAT fetch does); d = (float)q / 65535.0f;
+ *   4. d < 0.001f: a hit at that texel.  With e its emissive texel, sqrtf(e.x * e.x + e.y * e.y + e.z * e.z) > 0:
+ *      RC2DGI_RAY_EMISSIVE, rgba = (e.rgb, 1); otherwise RC2DGI_RAY_SURFACE, rgba = (color.rgb, _Reflectivity);
+ *   5. otherwise t += d.
+ * 32 texels read without an exit: RC2DGI_RAY_STEPS.  In the hit record, steps is the number of distRT texels read
+ * (0 .. 32); t the value that ended the loop (RC2DGI_RAY_STEPS: after the 32nd increment); (u, v) the last position
+ * evaluated; (ix, iy) the hit texel in GL order (row 0 at the bottom) or (-1, -1) without a hit; rgba (0, 0, 0, 1)
+ * for RANGE, EDGE and STEPS, the shader's initial `hit`.  The march is the same in every storage mode (distRT is the
+ * same 16-bit q, the inputs are floats in all three).
+ * A ray with a non-finite field or a field of magnitude above 2^20 is RC2DGI_RAY_INVALID: every other field of its
+ * record is 0, ix = iy = -1, and no memory is read.  Within that bound no position overflows or becomes NaN: t grows
+ * by at most 1 a step (d <= 1), so |t * dx| <= (2^20 + 32) * 2^20 < 2^41, asp <= 1, and the sum with |ox| <= 2^20 is
+ * far inside float range; every product and sum is of finite numbers.
+ *
+ * The host variants are synchronous w.r.t. the host pointers: they synchronise the context stream (a cascade chain
+ * timeout returns RC2DGI_E_DEVICE, as rc2dgi_compose does), run the kernel over context-owned device buffers and copy
+ * the results back.  The _device variants take device pointers on the context's device, enqueue the kernel on the
+ * context stream, after whatever frame is in flight, and return; the caller keeps the buffers alive until
+ * rc2dgi_sync().
+ * Errors, each leaving the context valid: RC2DGI_E_ARG for a null context, a null pointer with n > 0, n < 0 or
+ * n > 1 << 24, a bad `which` or `filter`, a device pointer not aligned to 8 bytes (uv), 16 (rgba) or 4 (rays, hits);
+ * RC2DGI_E_UNSUPPORTED for RC2DGI_FILTER_LINEAR on a texture other than GI1 / GI2 / BLUR / FINAL_GI and for any of
+ * the four calls on a row-strip shard (world > 1: its textures hold windows and bands); RC2DGI_E_STATE for a ray
+ * cast before the context's first completed frame (there is no distRT yet; sampling before a frame is allowed, as
+ * rc2dgi_compose allows it).  These calls only add exports: RC2DGI_ABI_VERSION stays 5. */
+int rc2dgi_sample(rc2dgi_ctx *ctx, int which, int filter, const float *uv, int n, float *rgba);
+int rc2dgi_sample_device(rc2dgi_ctx *ctx, int which, int filter, const void *uv_dev, int n, void *rgba_dev);
+
+typedef struct rc2dgi_ray {
+  float ox, oy;              /* origin, GL texture coordinates */
+  float dx, dy;              /* direction, used as given */
+  float t0, t1;              /* the interval marched */
+} rc2dgi_ray;                /* 24 bytes, blittable */
+typedef struct rc2dgi_rayhit {
+  int status;                /* RC2DGI_RAY_* */
+  int steps;                 /* distRT texels read */
+  int ix, iy;                /* the hit texel (GL order), or (-1, -1) */
+  float t, u, v;             /* where the loop ended */
+  float r, g, b, a;          /* the shader's hit record */
+} rc2dgi_rayhit;             /* 44 bytes, blittable */
+enum { RC2DGI_RAY_INVALID = -1, RC2DGI_RAY_RANGE = 0, RC2DGI_RAY_EDGE = 1, RC2DGI_RAY_EMISSIVE = 2,
+       RC2DGI_RAY_SURFACE = 3, RC2DGI_RAY_STEPS = 4 };
+int rc2dgi_raycast(rc2dgi_ctx *ctx, const rc2dgi_ray *rays, int n, rc2dgi_rayhit *hits);
+int rc2dgi_raycast_device(rc2dgi_ctx *ctx, const void *rays_dev, int n, void *hits_dev);
+
 /* cascade resolution (RC2DGI.cs:70-77), JFA step count (RC2DGI.cs:289-292) and which
  * giRT holds the final GI (1 or 2, RC2DGI.cs:365) */
 int rc2dgi_query(rc2dgi_ctx *ctx, int *cascade_w, int *cascade_h, int *jfa_steps, int *final_gi);

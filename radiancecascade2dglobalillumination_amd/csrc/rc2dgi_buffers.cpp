@@ -80,6 +80,10 @@ void free_buffers(rc2dgi_ctx *c) {
   if (c->present_buf) (void)hipFree(c->present_buf);
   c->present_buf = nullptr;
   c->present_cap = 0;
+  if (c->query_in) (void)hipFree(c->query_in);
+  if (c->query_out) (void)hipFree(c->query_out);
+  c->query_in = c->query_out = nullptr;
+  c->query_in_cap = c->query_out_cap = 0;
   void *bufs[] = {c->color_in, c->emissive, c->temp, c->color_out, c->jump1, c->jump2, c->dist, c->occ,
                   c->gi1,      c->gi2,      c->blur, c->dirs,      c->sky, c->gi_spare, c->dist_t, c->dist_p, c->dist_n, c->shade,
                   c->cmin,     c->dexit, c->hitc, c->dclr, c->dboxes, c->mfield, c->cell_pal, c->shade_list, c->jtail,

@@ -1,5 +1,6 @@
 // rc2dgi_compose.cpp -- the display frame of the C ABI (include/rc2dgi.h): the reference's display layout
-// (RC2DGI.cs:139-163), and the views resolved to their stored textures for k_present (rc2dgi_present.hip).
+// (RC2DGI.cs:139-163), and the views resolved to their stored textures for k_present (rc2dgi_present.hip).  The
+// queries too (rc2dgi_sample / rc2dgi_raycast, rc2dgi_query.hip): a point sample resolves its texture as a view does.
 #include "rc2dgi_ctx.h"
 
 namespace {
@@ -15,6 +16,88 @@ unsigned pack_rgba(const unsigned char *p) {
 }
 
 int clampi(long long v, int lo, int hi) { return (int)std::min<long long>(std::max<long long>(v, lo), hi); }
+
+// A render texture id and a filter resolved to source pointer, pitch, axes, storage kind and filter, as
+// rc2dgi_download reads that texture: what a compose view draws and a point sample fetches.  `tag` heads the message.
+int resolve_texture(rc2dgi_ctx *c, int which, int filter, const std::string &tag, TexSource &v) {
+  if (which < RC2DGI_RT_COLOR || which > RC2DGI_RT_FINAL_GI) return fail(c, RC2DGI_E_ARG, tag + "bad render texture id");
+  if (filter != RC2DGI_FILTER_RT && filter != RC2DGI_FILTER_POINT && filter != RC2DGI_FILTER_LINEAR)
+    return fail(c, RC2DGI_E_ARG, tag + "bad filter");
+  if (filter == RC2DGI_FILTER_LINEAR && !linear_rt(which))
+    return fail(c, RC2DGI_E_UNSUPPORTED, tag + "LINEAR is for GI1 / GI2 / BLUR / FINAL_GI");
+  v.linear = filter == RC2DGI_FILTER_LINEAR || (filter == RC2DGI_FILTER_RT && linear_rt(which));
+  if (which == RC2DGI_RT_FINAL_GI) which = (c->N % 2 == 0) ? RC2DGI_RT_GI2 : RC2DGI_RT_GI1;
+  const bool scr = !linear_rt(which);
+  v.nx = scr ? c->W : c->CW;
+  v.ny = scr ? c->H : c->CH;
+  v.powx = is_pow2(v.nx);
+  v.powy = is_pow2(v.ny);
+  v.pitch = scr ? c->sd.pitch : c->cd.pitch;
+  const bool u8 = rgba8(c);
+  const int gi_kind = u8 ? PK_U8 : (c->storage == RC2DGI_STORAGE_F16 ? PK_F16 : PK_F32);
+  switch (which) {
+    case RC2DGI_RT_COLOR: v.src = c->frame_done ? c->color_out : c->color_in; v.kind = PK_F32; break;
+    case RC2DGI_RT_EMISSIVE: v.src = c->emissive; v.kind = PK_F32; break;
+    case RC2DGI_RT_TEMP: v.src = c->temp; v.kind = PK_F32; break;
+    case RC2DGI_RT_JUMP1: v.src = c->jump1; v.kind = u8 ? PK_JUMP8 : PK_JUMP; break;
+    case RC2DGI_RT_JUMP2: v.src = c->jump2; v.kind = u8 ? PK_JUMP8 : PK_JUMP; break;
+    case RC2DGI_RT_DIST: v.src = c->dist; v.kind = u8 ? PK_DIST8 : PK_DIST; break;
+    case RC2DGI_RT_GI1: v.src = c->gi1; v.kind = gi_kind; break;
+    case RC2DGI_RT_GI2: v.src = c->gi2; v.kind = c->N == 1 ? PK_CONST : gi_kind; break;  // never drawn with one cascade
+    default: v.src = c->blur; v.kind = u8 ? PK_U8 : PK_F32; break;  // RC2DGI_RT_BLUR
+  }
+  return RC2DGI_OK;
+}
+
+// the checks the four query calls share; n == 0 is left to the caller (a successful no-op)
+int query_args(rc2dgi_ctx *c, const void *in, int n, const void *out) {
+  if (!c) return RC2DGI_E_ARG;
+  RC2DGI_USABLE(c);
+  if (n < 0 || n > kQueryMax) return fail(c, RC2DGI_E_ARG, "n is 0 .. 1 << 24");
+  if (n > 0 && (!in || !out)) return fail(c, RC2DGI_E_ARG, "null argument");
+  if (c->world > 1)
+    return fail(c, RC2DGI_E_UNSUPPORTED, "a row-strip shard's textures hold windows and bands: query an unsharded context");
+  return RC2DGI_OK;
+}
+
+int ray_scene(rc2dgi_ctx *c, RayScene &s) {
+  if (!c->have_frame) return fail(c, RC2DGI_E_STATE, "a ray cast marches the last frame's distRT: run a frame first");
+  const float mx = (float)std::max(c->W, c->H);
+  s = RayScene{c->dist, c->color_in, c->emissive, c->sd.pitch, c->W, is_pow2(c->W) ? 1 : 0, c->H, is_pow2(c->H) ? 1 : 0,
+               (float)c->W / mx, (float)c->H / mx, c->reflectivity};
+  return RC2DGI_OK;
+}
+
+// grow one of the context's query buffers (the stream is idle: nothing uses the old one)
+int query_buffer(rc2dgi_ctx *c, unsigned char *&buf, size_t &cap, size_t need) {
+  if (need <= cap) return RC2DGI_OK;
+  if (buf) HIPCHK(c, hipFree(buf));
+  buf = nullptr;
+  cap = 0;
+  HIPCHK(c, alloc(&buf, need));
+  cap = need;
+  return RC2DGI_OK;
+}
+
+// The host variants: synchronise, report a chain timeout, upload `in`, run `launch` over the context's buffers, copy
+// `out` back.
+template <class Launch>
+int query_host(rc2dgi_ctx *c, const void *in, size_t in_bytes, void *out, size_t out_bytes, Launch launch) {
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = check_chain(c)) return rc;
+  if (int rc = query_buffer(c, c->query_in, c->query_in_cap, in_bytes)) return rc;
+  if (int rc = query_buffer(c, c->query_out, c->query_out_cap, out_bytes)) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->query_in, in, in_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, launch(c->query_in, c->query_out));
+  HIPCHK(c, hipMemcpyAsync(out, c->query_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RC2DGI_OK;
+}
+
+bool aligned_to(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+
+static_assert(sizeof(rc2dgi_ray) == 24 && sizeof(rc2dgi_rayhit) == 44, "the query records are 24 and 44 bytes");
 
 // Validate the call and resolve every view to source pointer, pitch, axes, storage kind and filter, as
 // rc2dgi_download reads that texture.  Views that miss the window are dropped.
@@ -35,38 +118,13 @@ int resolve_views(rc2dgi_ctx *c, const rc2dgi_view *views, int n, int out_w, int
   a.clear = pack_rgba(clear ? clear : black);
   a.out_w = out_w;
   a.out_h = out_h;
-  const bool u8 = rgba8(c);
   for (int k = 0; k < n; ++k) {
     const rc2dgi_view &q = views[k];
     const std::string tag = "view " + std::to_string(k) + ": ";
     if (q.which < RC2DGI_RT_COLOR || q.which > RC2DGI_RT_FINAL_GI) return fail(c, RC2DGI_E_ARG, tag + "bad render texture id");
     if (q.w < 1 || q.h < 1) return fail(c, RC2DGI_E_ARG, tag + "w and h are at least 1");
-    if (q.filter != RC2DGI_FILTER_RT && q.filter != RC2DGI_FILTER_POINT && q.filter != RC2DGI_FILTER_LINEAR)
-      return fail(c, RC2DGI_E_ARG, tag + "bad filter");
-    if (q.filter == RC2DGI_FILTER_LINEAR && !linear_rt(q.which))
-      return fail(c, RC2DGI_E_UNSUPPORTED, tag + "LINEAR is for GI1 / GI2 / BLUR / FINAL_GI");
     PresentView v{};
-    v.linear = q.filter == RC2DGI_FILTER_LINEAR || (q.filter == RC2DGI_FILTER_RT && linear_rt(q.which));
-    int which = q.which;
-    if (which == RC2DGI_RT_FINAL_GI) which = (c->N % 2 == 0) ? RC2DGI_RT_GI2 : RC2DGI_RT_GI1;
-    const bool scr = !linear_rt(which);
-    v.nx = scr ? c->W : c->CW;
-    v.ny = scr ? c->H : c->CH;
-    v.powx = is_pow2(v.nx);
-    v.powy = is_pow2(v.ny);
-    v.pitch = scr ? c->sd.pitch : c->cd.pitch;
-    const int gi_kind = u8 ? PK_U8 : (c->storage == RC2DGI_STORAGE_F16 ? PK_F16 : PK_F32);
-    switch (which) {
-      case RC2DGI_RT_COLOR: v.src = c->frame_done ? c->color_out : c->color_in; v.kind = PK_F32; break;
-      case RC2DGI_RT_EMISSIVE: v.src = c->emissive; v.kind = PK_F32; break;
-      case RC2DGI_RT_TEMP: v.src = c->temp; v.kind = PK_F32; break;
-      case RC2DGI_RT_JUMP1: v.src = c->jump1; v.kind = u8 ? PK_JUMP8 : PK_JUMP; break;
-      case RC2DGI_RT_JUMP2: v.src = c->jump2; v.kind = u8 ? PK_JUMP8 : PK_JUMP; break;
-      case RC2DGI_RT_DIST: v.src = c->dist; v.kind = u8 ? PK_DIST8 : PK_DIST; break;
-      case RC2DGI_RT_GI1: v.src = c->gi1; v.kind = gi_kind; break;
-      case RC2DGI_RT_GI2: v.src = c->gi2; v.kind = c->N == 1 ? PK_CONST : gi_kind; break;  // never drawn with one cascade
-      default: v.src = c->blur; v.kind = u8 ? PK_U8 : PK_F32; break;  // RC2DGI_RT_BLUR
-    }
+    if (int rc = resolve_texture(c, q.which, q.filter, tag, v)) return rc;
     v.x = q.x;
     v.y = q.y;
     v.w = q.w;
@@ -144,6 +202,49 @@ int rc2dgi_compose(rc2dgi_ctx *c, const rc2dgi_view *views, int n, int out_w, in
                              hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RC2DGI_OK;
+}
+
+// ---- queries (rc2dgi_query.hip)
+int rc2dgi_sample_device(rc2dgi_ctx *c, int which, int filter, const void *uv_dev, int n, void *rgba_dev) {
+  if (int rc = query_args(c, uv_dev, n, rgba_dev)) return rc;
+  TexSource t{};
+  if (int rc = resolve_texture(c, which, filter, "sample: ", t)) return rc;
+  if (n == 0) return RC2DGI_OK;
+  if (!aligned_to(uv_dev, 8) || !aligned_to(rgba_dev, 16))
+    return fail(c, RC2DGI_E_ARG, "the points are aligned to 8 bytes and the results to 16");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, launch_sample(t, uv_dev, n, rgba_dev, c->stream));
+  return RC2DGI_OK;
+}
+
+int rc2dgi_sample(rc2dgi_ctx *c, int which, int filter, const float *uv, int n, float *rgba) {
+  if (int rc = query_args(c, uv, n, rgba)) return rc;
+  TexSource t{};
+  if (int rc = resolve_texture(c, which, filter, "sample: ", t)) return rc;
+  if (n == 0) return RC2DGI_OK;
+  return query_host(c, uv, (size_t)n * 8, rgba, (size_t)n * 16,
+                    [&](void *in, void *out) { return launch_sample(t, in, n, out, c->stream); });
+}
+
+int rc2dgi_raycast_device(rc2dgi_ctx *c, const void *rays_dev, int n, void *hits_dev) {
+  if (int rc = query_args(c, rays_dev, n, hits_dev)) return rc;
+  RayScene s{};
+  if (int rc = ray_scene(c, s)) return rc;
+  if (n == 0) return RC2DGI_OK;
+  if (!aligned_to(rays_dev, 4) || !aligned_to(hits_dev, 4))
+    return fail(c, RC2DGI_E_ARG, "the rays and the hit records are aligned to 4 bytes");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, launch_raycast(s, rays_dev, n, hits_dev, c->stream));
+  return RC2DGI_OK;
+}
+
+int rc2dgi_raycast(rc2dgi_ctx *c, const rc2dgi_ray *rays, int n, rc2dgi_rayhit *hits) {
+  if (int rc = query_args(c, rays, n, hits)) return rc;
+  RayScene s{};
+  if (int rc = ray_scene(c, s)) return rc;
+  if (n == 0) return RC2DGI_OK;
+  return query_host(c, rays, (size_t)n * sizeof(rc2dgi_ray), hits, (size_t)n * sizeof(rc2dgi_rayhit),
+                    [&](void *in, void *out) { return launch_raycast(s, in, n, out, c->stream); });
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // rc2dgi_ctx.h -- the context behind the C ABI (include/rc2dgi.h) and the helpers its host units share:
 // rc2dgi_buffers.cpp (sizes, allocation, tables), rc2dgi_frame.cpp (the frame), rc2dgi_group.cpp (RCCL, sharded
-// groups), rc2dgi_autotune.cpp, rc2dgi_compose.cpp (the display frame) and rc2dgi_capi.cpp (everything else of the ABI).
+// groups), rc2dgi_autotune.cpp, rc2dgi_compose.cpp (the display frame and the queries) and rc2dgi_capi.cpp (everything
+// else of the ABI).
 #pragma once
 #include "../../include/rc2dgi.h"
 
@@ -21,6 +22,7 @@
 #include "rc2dgi_kernels.h"
 #include "rc2dgi_paint.h"
 #include "rc2dgi_present.h"
+#include "rc2dgi_query.h"
 #include "rc2dgi_shard.h"
 #include "rc2dgi_tuning.h"
 
@@ -114,6 +116,8 @@ struct rc2dgi_ctx : rc2dgi::Tuning {
   PaintBuffers paint_buf;  // rc2dgi_paint primitive setup
   unsigned char *present_buf = nullptr;  // rc2dgi_compose's window image (RGBA8), grown on demand
   size_t present_cap = 0;
+  unsigned char *query_in = nullptr, *query_out = nullptr;  // rc2dgi_sample / rc2dgi_raycast's points or rays and
+  size_t query_in_cap = 0, query_out_cap = 0;               // their results, grown on demand
   int rank = 0, world = 1;
   int ow0 = 0, ow1 = 0;  // screen rows tempRT / the merged colorRT hold (their row 0 = row ow0): [0, H), or a row-strip
                          // shard's own rows (out_buffers)

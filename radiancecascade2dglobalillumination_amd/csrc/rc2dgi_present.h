@@ -9,7 +9,7 @@
 
 namespace rc2dgi {
 
-// how a view's texture is stored (what a texel fetch decodes)
+// how a render texture is stored (what a texel fetch decodes)
 enum PresentKind {
   PK_F32 = 0,    // float4
   PK_F16 = 1,    // RGBA16F (giRT1 / giRT2 of RC2DGI_STORAGE_F16)
@@ -21,14 +21,20 @@ enum PresentKind {
   PK_CONST = 7   // (0, 0, 0, 1): giRT2 with one cascade (ClearAllRTs content)
 };
 
-// one view, resolved on the host: the source in its stored format and the rectangles the kernel tests
-struct PresentView {
+// a render texture resolved on the host (resolve_texture, rc2dgi_compose.cpp): the source in its stored format, as
+// rc2dgi_download reads it.  What k_present fetches for a view and k_sample (rc2dgi_query.hip) for a point; the
+// decoder of both is rc2dgi_texel.h.
+struct TexSource {
   const void *src;
   int pitch;           // texels a row
   int nx, powx;        // texture width, and whether it is a power of two (GL wrap arithmetic differs)
   int ny, powy;
   int kind;            // PresentKind
   int linear;          // LINEAR filter (else POINT)
+};
+
+// one view, resolved on the host: its texture and the rectangles the kernel tests
+struct PresentView : TexSource {
   int x, y, w, h;      // the view's rectangle as given (may hang over the window)
   unsigned border;     // r | g << 8 | b << 16 | a << 24; a == 0: none
   int cx0, cx1, cy0, cy1;  // the rectangle clipped to the window, [c*0, c*1)

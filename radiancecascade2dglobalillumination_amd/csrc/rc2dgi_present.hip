@@ -4,7 +4,8 @@
 // (RC2DGI.cs:135-165, DrawTexturePro with a negative source height, 435-448).  k_present restates those draws for
 // a list of views: every window pixel starts as the clear colour and takes, view by view, the view's sampled texel
 // and then its border colour, each blended in 8 bits as the RGBA8 passes blend (GiU8::blend, rc2dgi_device.h).
-// A texel is decoded from the texture's stored format to the value rc2dgi_download returns for it.
+// A texel is decoded from the texture's stored format to the value rc2dgi_download returns for it (present_texel /
+// present_sample, rc2dgi_texel.h, shared with the point samples of rc2dgi_query.hip).
 //
 // A lane owns four consecutive pixels of one row (one 16-byte store; a wave covers 256 pixels of a row, a workgroup
 // 1024).  Where those four are covered by exactly one view and that view is a 1:1 POINT view of float4 or RGBA8
@@ -16,6 +17,7 @@
 // (4096^2: 87 us against 58 us, 1200x900: 14 against 9.5; profiles/present/nt_ab.json).
 #include "rc2dgi_present.h"
 #include "rc2dgi_device.h"
+#include "rc2dgi_texel.h"
 
 namespace rc2dgi {
 
@@ -31,56 +33,6 @@ __device__ __forceinline__ unsigned blend8(unsigned s, unsigned d) {
     o |= (v < 255u ? v : 255u) << k;
   }
   return o;
-}
-
-// the value of texel (i, j), 0 <= i < nx, 0 <= j < ny, as rc2dgi_download returns it
-__device__ __forceinline__ float4 present_texel(const PresentView &v, int i, int j) {
-  const size_t o = (size_t)j * v.pitch + i;
-  switch (v.kind) {
-    case PK_F32: return static_cast<const float4 *>(v.src)[o];
-    case PK_F16: return GiF16::ld(static_cast<const uint2 *>(v.src) + o);
-    case PK_U8: return GiU8::ld(static_cast<const unsigned *>(v.src) + o);
-    case PK_JUMP: {
-      const unsigned s = static_cast<const unsigned *>(v.src)[o];
-      if (s == 0x80008000u) return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-      return make_float4(((float)(int)(s & 0xFFFFu) + 0.5f) / (float)v.nx, ((float)(int)(s >> 16) + 0.5f) / (float)v.ny,
-                         0.0f, 1.0f);
-    }
-    case PK_JUMP8: {
-      const unsigned s = static_cast<const unsigned *>(v.src)[o];
-      return make_float4((float)(s & 0xFFFFu) * kInv255, (float)(s >> 16) * kInv255, 0.0f, 1.0f);
-    }
-    case PK_DIST:
-    case PK_DIST8: {
-      const unsigned d = static_cast<const unsigned short *>(v.src)[o];
-      const float hi = (float)((d >> 8) & 255u), lo = (float)(d & 255u);
-      return v.kind == PK_DIST8 ? make_float4(hi * kInv255, lo * kInv255, 0.0f, 1.0f)
-                                : make_float4(hi / 255.0f, lo / 255.0f, 0.0f, 1.0f);
-    }
-    default: return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-  }
-}
-
-// texture(T, (u, v)) of a view: POINT, or LINEAR with the bilerp of the texture's storage
-__device__ __forceinline__ float4 present_sample(const PresentView &v, float tu, float tv) {
-  const Axis ax{v.nx, v.powx}, ay{v.ny, v.powy};
-  if (!v.linear || v.kind == PK_CONST) return present_texel(v, wrap_nearest(tu, ax), wrap_nearest(tv, ay));
-  int x0, x1, y0, y1;
-  float wx, wy;
-  wrap_linear(tu, ax, x0, x1, wx);
-  wrap_linear(tv, ay, y0, y1, wy);
-  const size_t r0 = (size_t)y0 * v.pitch, r1 = (size_t)y1 * v.pitch;
-  if (v.kind == PK_U8) {
-    const unsigned *T = static_cast<const unsigned *>(v.src);
-    return GiU8::bilerp(T[r0 + x0], T[r0 + x1], T[r1 + x0], T[r1 + x1], wx, wy);
-  }
-  if (v.kind == PK_F16) {
-    const uint2 *T = static_cast<const uint2 *>(v.src);
-    return GiF32::bilerp(GiF16::ld(T + r0 + x0), GiF16::ld(T + r0 + x1), GiF16::ld(T + r1 + x0), GiF16::ld(T + r1 + x1),
-                         wx, wy);
-  }
-  const float4 *T = static_cast<const float4 *>(v.src);  // PK_F32 (the host admits LINEAR on no other kind)
-  return GiF32::bilerp(T[r0 + x0], T[r0 + x1], T[r1 + x0], T[r1 + x1], wx, wy);
 }
 
 // The plain-blit test for pixels [x0, x1) of row py: exactly one view's clipped rectangle meets them, and they lie

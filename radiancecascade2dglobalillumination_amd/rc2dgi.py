@@ -67,6 +67,36 @@ class View(ctypes.Structure):
                    *(int(v) for v in border))
 
 
+class Ray(ctypes.Structure):
+    """rc2dgi_ray: origin and direction in GL texture coordinates (the direction is used as given) and the
+    interval [t0, t1] marched."""
+    _fields_ = [("ox", ctypes.c_float), ("oy", ctypes.c_float), ("dx", ctypes.c_float), ("dy", ctypes.c_float),
+                ("t0", ctypes.c_float), ("t1", ctypes.c_float)]
+
+
+class RayHit(ctypes.Structure):
+    """rc2dgi_rayhit: how a ray ended (RAY_*), the distRT texels it read, the hit texel (GL order) or (-1, -1), where
+    the loop ended (t, u, v) and the shader's hit record (r, g, b, a)."""
+    _fields_ = [("status", ctypes.c_int), ("steps", ctypes.c_int), ("ix", ctypes.c_int), ("iy", ctypes.c_int),
+                ("t", ctypes.c_float), ("u", ctypes.c_float), ("v", ctypes.c_float), ("r", ctypes.c_float),
+                ("g", ctypes.c_float), ("b", ctypes.c_float), ("a", ctypes.c_float)]
+
+
+RAY_INVALID, RAY_RANGE, RAY_EDGE, RAY_EMISSIVE, RAY_SURFACE, RAY_STEPS = -1, 0, 1, 2, 3, 4
+RAY_DTYPE = np.dtype([(n, np.float32) for n, _ in Ray._fields_])
+HIT_DTYPE = np.dtype([(n, np.int32 if t is ctypes.c_int else np.float32) for n, t in RayHit._fields_])
+HIT_INT_FIELDS = 4  # status, steps, ix, iy; the seven float fields follow
+QUERY_MAX = 1 << 24
+
+
+def hit_floats(hits):
+    """The float fields (t, u, v, r, g, b, a) of the int32 (n, 11) tensor RC2DGI.raycast returns for device rays: a
+    float32 (n, 7) view of the same memory."""
+    import torch
+
+    return hits[:, HIT_INT_FIELDS:].view(torch.float32)
+
+
 def _view_array(views):
     arr = (View * max(len(views), 1))()
     for k, v in enumerate(views):
@@ -146,6 +176,10 @@ def load_library(path: Optional[str] = None):
                             ctypes.POINTER(ctypes.c_ubyte), vp, ctypes.c_int], ctypes.c_int),
         "rc2dgi_compose_device": ([vp, ctypes.POINTER(View), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    ctypes.POINTER(ctypes.c_ubyte), vp, ctypes.c_int], ctypes.c_int),
+        "rc2dgi_sample": ([vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp], ctypes.c_int),
+        "rc2dgi_sample_device": ([vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp], ctypes.c_int),
+        "rc2dgi_raycast": ([vp, vp, ctypes.c_int, vp], ctypes.c_int),
+        "rc2dgi_raycast_device": ([vp, vp, ctypes.c_int, vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -375,6 +409,66 @@ class RC2DGI:
         views = display_layout(self.screen_width, self.screen_height)
         return self.compose(views if thumbnails else views[:1])
 
+    # ---------------------------------------------------------------- queries: a few values, no texture download
+    def _on_device(self, t, what):
+        if not getattr(t, "is_cuda", False) or t.device.index != self.device:
+            raise TypeError(f"{what}: expected a tensor on this context's GPU")
+        if str(t.dtype) != "torch.float32" or not t.is_contiguous():
+            raise TypeError(f"{what}: expected a contiguous float32 tensor")
+
+    def sample(self, which, uv, filter=FILTER_RT):
+        """texture(T, (u, v)) for n points (rc2dgi_sample): which -- a name of RT or an rc2dgi_rt id; uv (n, 2)
+        float32 in GL texture coordinates (v up; the centre of y-down pixel (x, y) is ((x + .5) / W,
+        1 - (y + .5) / H)).  A numpy array returns numpy (n, 4) float32, synchronously.  A contiguous torch tensor on
+        this context's GPU enqueues the kernel on the context stream (rc2dgi_sample_device) and returns a new (n, 4)
+        tensor there: order the stream or sync() before reading, as with compose_into."""
+        w = RT[which] if isinstance(which, str) else int(which)
+        if hasattr(uv, "data_ptr"):
+            import torch
+
+            self._on_device(uv, "sample")
+            if uv.dim() != 2 or uv.shape[1] != 2:
+                raise ValueError(f"sample: expected (n, 2) points, got {tuple(uv.shape)}")
+            out = torch.empty((uv.shape[0], 4), dtype=torch.float32, device=uv.device)
+            self._check(self._L.rc2dgi_sample_device(self._h, w, int(filter), ctypes.c_void_p(uv.data_ptr()),
+                                                     int(uv.shape[0]), ctypes.c_void_p(out.data_ptr())), "sample")
+            return out
+        a = np.ascontiguousarray(uv, np.float32)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError(f"sample: expected (n, 2) points, got {a.shape}")
+        out = np.empty((a.shape[0], 4), np.float32)
+        self._check(self._L.rc2dgi_sample(self._h, w, int(filter), a.ctypes.data_as(ctypes.c_void_p), a.shape[0],
+                                          out.ctypes.data_as(ctypes.c_void_p)), "sample")
+        return out
+
+    def raycast(self, rays):
+        """SampleRadianceSDF (RadianceCascades.fs:60-92) for n rays over the last frame (rc2dgi_raycast): rays
+        (n, 6) float32 (ox, oy, dx, dy, t0, t1) or a structured array of RAY_DTYPE.  numpy in: a structured array of
+        HIT_DTYPE out (status, steps, ix, iy, t, u, v, r, g, b, a), synchronously.  A contiguous (n, 6) torch tensor
+        on this context's GPU enqueues the kernel on the context stream (rc2dgi_raycast_device) and returns a new
+        int32 (n, 11) tensor there, the records' words; hit_floats(hits) views its float fields."""
+        if hasattr(rays, "data_ptr"):
+            import torch
+
+            self._on_device(rays, "raycast")
+            if rays.dim() != 2 or rays.shape[1] != 6:
+                raise ValueError(f"raycast: expected (n, 6) rays, got {tuple(rays.shape)}")
+            out = torch.empty((rays.shape[0], 11), dtype=torch.int32, device=rays.device)
+            self._check(self._L.rc2dgi_raycast_device(self._h, ctypes.c_void_p(rays.data_ptr()), int(rays.shape[0]),
+                                                      ctypes.c_void_p(out.data_ptr())), "raycast")
+            return out
+        a = np.asarray(rays)
+        if a.dtype == RAY_DTYPE:
+            a = np.ascontiguousarray(a).reshape(-1)
+        else:
+            a = np.ascontiguousarray(a, np.float32)
+            if a.ndim != 2 or a.shape[1] != 6:
+                raise ValueError(f"raycast: expected (n, 6) rays, got {a.shape}")
+        out = np.empty(a.shape[0], HIT_DTYPE)
+        self._check(self._L.rc2dgi_raycast(self._h, a.ctypes.data_as(ctypes.c_void_p), a.shape[0],
+                                           out.ctypes.data_as(ctypes.c_void_p)), "raycast")
+        return out
+
     def set_tuning(self, key: str, value: int) -> None:
         """Performance knobs (results are identical for every value), e.g. rc_variant."""
         self._check(self._L.rc2dgi_set_tuning(self._h, key.encode(), int(value)), f"set_tuning {key}")
@@ -590,4 +684,6 @@ def plan_jfa_window(W: int, H: int, N: int, rank: int, world: int, step: int, re
 
 __all__ = ["RC2DGI", "RC2DGIError", "load_library", "abi_version", "RT", "PASS_NAMES", "shard_unique_id", "do_group",
            "plan_rows", "plan_jfa_exchange", "plan_jfa_window", "PLAN_JFA", "PLAN_LEVEL", "PLAN_BLUR", "PLAN_MERGE",
-           "View", "display_layout", "FILTER_RT", "FILTER_POINT", "FILTER_LINEAR", "MAX_VIEWS"]
+           "View", "display_layout", "FILTER_RT", "FILTER_POINT", "FILTER_LINEAR", "MAX_VIEWS", "Ray", "RayHit",
+           "RAY_DTYPE", "HIT_DTYPE", "hit_floats", "RAY_INVALID", "RAY_RANGE", "RAY_EDGE", "RAY_EMISSIVE", "RAY_SURFACE",
+           "RAY_STEPS"]
