@@ -1,6 +1,7 @@
 /* layout.c -- sizeof / offsetof of the ABI structs, as the C compiler lays them out, for
  * tests/test_host_cpu.py to compare with the C# StructLayout(Sequential) mirrors in
- * host/csharp/RC2DGINative.cs (Config, Prim; View: tests/test_present_cpu.py; Ray, RayHit: tests/test_query_cpu.py). */
+ * host/csharp/RC2DGINative.cs (Config, Prim; View: tests/test_present_cpu.py; Ray, RayHit: tests/test_query_cpu.py;
+ * Rect, Stats: tests/test_reduce_cpu.py). */
 #include <stddef.h>
 #include <stdio.h>
 
@@ -59,5 +60,17 @@ int main(void) {
   F(rc2dgi_rayhit, g);
   F(rc2dgi_rayhit, b);
   F(rc2dgi_rayhit, a);
+  printf("rc2dgi_rect %zu\n", sizeof(rc2dgi_rect));
+  F(rc2dgi_rect, x);
+  F(rc2dgi_rect, y);
+  F(rc2dgi_rect, w);
+  F(rc2dgi_rect, h);
+  printf("rc2dgi_stats %zu\n", sizeof(rc2dgi_stats));
+  F(rc2dgi_stats, status);
+  F(rc2dgi_stats, texels);
+  F(rc2dgi_stats, nonfinite);
+  F(rc2dgi_stats, min);
+  F(rc2dgi_stats, max);
+  F(rc2dgi_stats, sum);
   return 0;
 }

@@ -90,6 +90,27 @@ static unsafe class RC2DGINative
     [DllImport(Lib)] public static extern int rc2dgi_raycast(IntPtr ctx, Ray* rays, int n, RayHit* hits);
     [DllImport(Lib)] public static extern int rc2dgi_raycast_device(IntPtr ctx, void* raysDev, int n, void* hitsDev);
 
+    // Region statistics: rectangles of a render texture measured without a Download.  Per rectangle and channel the
+    // count of NaN / infinite values, min and max of the finite ones and their double sum in the header's fixed order
+    // (the same bits on every run).  rects is host memory in both variants.  (rc2dgi_rect is TexRect here: this class
+    // already has a Rect, the primitive's constructor.)
+    [StructLayout(LayoutKind.Sequential, Size = 16)]
+    public struct TexRect
+    {
+        public int X, Y, W, H;         // texels of that texture, GL order (row 0 = bottom)
+    }
+    [StructLayout(LayoutKind.Sequential, Size = 88)]
+    public struct Stats
+    {
+        public int Status;             // 0, or -1: the rectangle does not lie inside the texture (all else 0)
+        public int Texels;             // w * h
+        public fixed int Nonfinite[4]; // per channel r, g, b, a: values that are NaN or +-inf
+        public fixed float Min[4], Max[4];
+        public fixed double Sum[4];    // offset 56; Sum[c] / (Texels - Nonfinite[c]) is the mean
+    }
+    [DllImport(Lib)] public static extern int rc2dgi_reduce(IntPtr ctx, int which, TexRect* rects, int n, Stats* stats);
+    [DllImport(Lib)] public static extern int rc2dgi_reduce_device(IntPtr ctx, int which, TexRect* rects, int n, void* statsDev);
+
     static IntPtr ctx;
     static Config config;
     static byte[] scratch = Array.Empty<byte>();
@@ -181,6 +202,27 @@ static unsafe class RC2DGINative
         RayHit hit;
         Check(rc2dgi_raycast(ctx, &ray, 1, &hit), "raycast");
         return hit.Status == (int)RayStatus.Range;
+    }
+
+    // The light arriving at a sprite: the mean of the final GI over the window rectangle it covers (y down), from one
+    // region reduction instead of a Download.  The rectangle is clipped to the texture; empty: zero.
+    public static System.Numerics.Vector4 MeanLight(Rectangle sprite)
+    {
+        Check(rc2dgi_query(ctx, out int cw, out int ch, out _, out _), "query");
+        float sx = cw / (float)config.ScreenWidth, sy = ch / (float)config.ScreenHeight;
+        int x0 = Math.Clamp((int)MathF.Floor(sprite.X * sx), 0, cw), x1 = Math.Clamp((int)MathF.Ceiling((sprite.X + sprite.Width) * sx), 0, cw);
+        int y0 = Math.Clamp((int)MathF.Floor(sprite.Y * sy), 0, ch), y1 = Math.Clamp((int)MathF.Ceiling((sprite.Y + sprite.Height) * sy), 0, ch);
+        if (x1 <= x0 || y1 <= y0) return System.Numerics.Vector4.Zero;
+        var rect = new TexRect { X = x0, Y = ch - y1, W = x1 - x0, H = y1 - y0 };  // row 0 of the texture is the bottom
+        Stats st;
+        Check(rc2dgi_reduce(ctx, (int)RT.FinalGI, &rect, 1, &st), "reduce");
+        var m = new float[4];
+        for (int c = 0; c < 4; ++c)
+        {
+            int finite = st.Texels - st.Nonfinite[c];
+            m[c] = finite > 0 ? (float)(st.Sum[c] / finite) : 0f;
+        }
+        return new System.Numerics.Vector4(m[0], m[1], m[2], m[3]);
     }
 
     public static Prim Rect(Rectangle r, Color c) => new Prim { Kind = 0, X = r.X, Y = r.Y, W = r.Width, H = r.Height, R = c.R, G = c.G, B = c.B, A = c.A };

@@ -62,7 +62,7 @@ typedef enum rc2dgi_status {
   RC2DGI_E_STATE = -6,        /* call not valid in the current state */
   RC2DGI_E_DEVICE = -7        /* a device-side check failed: an enqueued frame's results are wrong (the cascade
                                  chain's wait timed out; reported by the next rc2dgi_sync / _download /
-                                 _download_level / _compose / _do / _do_phase) */
+                                 _download_level / _compose / _reduce / _do / _do_phase) */
 } rc2dgi_status;
 
 typedef enum rc2dgi_storage {
@@ -278,6 +278,70 @@ enum { RC2DGI_RAY_INVALID = -1, RC2DGI_RAY_RANGE = 0, RC2DGI_RAY_EDGE = 1, RC2DG
 int rc2dgi_raycast(rc2dgi_ctx *ctx, const rc2dgi_ray *rays, int n, rc2dgi_rayhit *hits);
 int rc2dgi_raycast_device(rc2dgi_ctx *ctx, const void *rays_dev, int n, void *hits_dev);
 
+/* ---- region statistics: rectangles of a render texture measured without downloading it.  (The light arriving at a
+ * sprite: the mean of FINAL_GI over the sprite's texels; an exposure: the maximum and mean of FINAL_GI; health: the
+ * count of NaN and infinite texels.)  For each of n rectangles and each channel: how many values are not finite, the
+ * smallest and the largest finite value, and the float64 sum of the finite values in ONE fixed order, so that a
+ * result is the same bits on every run and equals a restatement on the host.
+ *
+ * Texture and rectangle.
+ *   which    any rc2dgi_rt, RC2DGI_RT_FINAL_GI included.
+ *   Texels   a texel's value is what rc2dgi_download returns for it as floats -- the list under rc2dgi_compose (JUMP1 /
+ *            JUMP2 decoded, DIST its hi / lo bytes, COLOR the input before the first frame and the merged output
+ *            after, GI2 (0, 0, 0, 1) with one cascade), through the decoder the views and the point samples use: a
+ *            1 x 1 rectangle equals a RC2DGI_FILTER_POINT sample at that texel's centre.
+ *   rect     texels of that texture in GL order (row 0 = the bottom, as rc2dgi_download returns them).  With TW x TH
+ *            the texture's size, a rectangle is valid when w >= 1, h >= 1, x >= 0, y >= 0, w <= TW - x and
+ *            h <= TH - y (compared in this form: nothing overflows, whatever the four ints hold).  Any other
+ *            rectangle yields status = RC2DGI_STATS_INVALID with every other field 0 and reads no texture memory;
+ *            the other records of the array are unaffected.  There is no wrap and no clipping.
+ *
+ * Per channel (r, g, b, a = 0 .. 3).
+ *   Each value enters as x + 0.0f: -0.0 becomes +0.0 and nothing else changes.  Subnormals are values like any other
+ *   (not flushed).  A NaN or +-inf is counted in nonfinite[c] and takes no part in min, max or sum of that channel.
+ *   min / max are the smallest and the largest finite value (every order gives the same result: no -0.0 is left).
+ *   With no finite value in the channel, min = +inf, max = -inf and sum = 0.0.
+ *
+ * The sum is float64 in one fixed order.
+ *   Leaf (i, j), 0 <= i < w, 0 <= j < h, is the exact conversion to double of that finite value, or +0.0 for an
+ *   excluded one.
+ *   A row is reduced by the adjacent-pair tree over P = the smallest power of two >= w leaves, the leaves from w up
+ *   being +0.0: level by level s[i] = s[2i] + s[2i+1], until one value is left.
+ *   The h row sums are reduced by the same tree, padded to the power of two >= h.
+ *   No leaf is -0.0 and no sum of these can be, so x + 0.0 == x everywhere: an implementation may skip all-padding
+ *   subtrees and use a + b == b + a freely.  Equivalently: a sequence of length 1 is its value, a longer one splits
+ *   at the largest power of two below its length into left + right.
+ *   Nothing overflows: |v| < 2^128 and there are at most 2^30 leaves.
+ *   sum[c] / (texels - nonfinite[c]) is the mean of the finite values; the library does not divide.
+ *
+ * Calls.  `rects` is host memory in both variants, read only during the call (as the views of rc2dgi_compose_device
+ * and the primitives of rc2dgi_paint are): the host validates the rectangles and plans the work from them.
+ * rc2dgi_reduce synchronises the context stream (a cascade chain timeout returns RC2DGI_E_DEVICE, as rc2dgi_compose
+ * does), runs the kernels over context-owned device buffers and copies the n records back.  rc2dgi_reduce_device
+ * enqueues the kernels on the context stream, after whatever frame is in flight, and returns.  Up to 4 rectangles
+ * travel in the kernels' arguments; a longer list is planned into host memory and copied stream-ordered, a batch at a
+ * time, as rc2dgi_paint copies its primitives: the runtime may stage such a copy from pageable memory or wait for it
+ * on the host, so with a long list the call may return only when the work queued before it has run (not measured).
+ * stats_dev is a device pointer on the context's device, aligned to 8 bytes, with room for n records, that the
+ * caller keeps alive until rc2dgi_sync().  Reducing before the first frame is allowed, as sampling is (COLOR is then
+ * the input).  n == 0 is a successful no-op.
+ * Errors, each leaving the context valid: RC2DGI_E_ARG for a null context, a null pointer with n > 0, n < 0 or
+ * n > 1 << 20, a bad `which`, a stats_dev not aligned to 8 bytes; RC2DGI_E_UNSUPPORTED on a row-strip shard
+ * (world > 1: its textures hold windows and bands).  These calls only add exports: RC2DGI_ABI_VERSION stays 5. */
+typedef struct rc2dgi_rect {
+  int x, y, w, h;            /* texels of that texture, GL order (row 0 = bottom) */
+} rc2dgi_rect;               /* 16 bytes, blittable */
+enum { RC2DGI_STATS_OK = 0, RC2DGI_STATS_INVALID = -1 };
+typedef struct rc2dgi_stats {
+  int status;                /* RC2DGI_STATS_* */
+  int texels;                /* w * h */
+  int nonfinite[4];          /* per channel r, g, b, a: values that are NaN or +-inf */
+  float min[4], max[4];      /* of the finite values */
+  double sum[4];             /* offset 56: of the finite values, in the order above */
+} rc2dgi_stats;              /* 88 bytes, 8-byte aligned, blittable */
+int rc2dgi_reduce(rc2dgi_ctx *ctx, int which, const rc2dgi_rect *rects, int n, rc2dgi_stats *stats);
+int rc2dgi_reduce_device(rc2dgi_ctx *ctx, int which, const rc2dgi_rect *rects, int n, void *stats_dev);
+
 /* cascade resolution (RC2DGI.cs:70-77), JFA step count (RC2DGI.cs:289-292) and which
  * giRT holds the final GI (1 or 2, RC2DGI.cs:365) */
 int rc2dgi_query(rc2dgi_ctx *ctx, int *cascade_w, int *cascade_h, int *jfa_steps, int *final_gi);
@@ -346,7 +410,8 @@ int rc2dgi_set_sky_table(rc2dgi_ctx *ctx, const float *rgb, int n);
  *                     starting when the upper tiles under its footprint are written (2: unrolled march);
  *                     4: the top level in that launch too; f32 cascades, one process.  A wait that times out
  *                     makes the next rc2dgi_sync / rc2dgi_download / rc2dgi_download_level / rc2dgi_compose /
- *                     rc2dgi_do / rc2dgi_do_phase return RC2DGI_E_DEVICE and turns the chain off for the context
+ *                     rc2dgi_reduce / rc2dgi_do / rc2dgi_do_phase return RC2DGI_E_DEVICE and turns the chain off for
+ *                     the context
  *                     (never a silent wrong frame)
  *   "rc_chain_spin"   diagnostic: polls per chain wait (0: the default bound; -1: every wait times out at once)
  *   "jfa_rows"        0 (default), 4, 8: the short isotropic JumpFlood steps (offsets 1, 2, 4 on square power-of-two

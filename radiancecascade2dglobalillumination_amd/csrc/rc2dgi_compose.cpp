@@ -1,7 +1,10 @@
 // rc2dgi_compose.cpp -- the display frame of the C ABI (include/rc2dgi.h): the reference's display layout
 // (RC2DGI.cs:139-163), and the views resolved to their stored textures for k_present (rc2dgi_present.hip).  The
-// queries too (rc2dgi_sample / rc2dgi_raycast, rc2dgi_query.hip): a point sample resolves its texture as a view does.
+// queries too (rc2dgi_sample / rc2dgi_raycast, rc2dgi_query.hip): a point sample resolves its texture as a view does,
+// and so do the region statistics (rc2dgi_reduce, rc2dgi_reduce.hip), whose rectangles are planned here.
 #include "rc2dgi_ctx.h"
+
+#include <cstddef>
 
 namespace {
 
@@ -98,6 +101,131 @@ int query_host(rc2dgi_ctx *c, const void *in, size_t in_bytes, void *out, size_t
 bool aligned_to(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 static_assert(sizeof(rc2dgi_ray) == 24 && sizeof(rc2dgi_rayhit) == 44, "the query records are 24 and 44 bytes");
+
+// ---- region statistics (rc2dgi_reduce.hip): the host validates the rectangles and cuts them into work items
+
+static_assert(sizeof(rc2dgi_rect) == 16 && sizeof(rc2dgi_stats) == 88 && offsetof(rc2dgi_stats, sum) == 56,
+              "the region records are 16 and 88 bytes");
+
+// the device side of one batch: [items, then joins | band partials], a fixed size whatever the call
+constexpr size_t kReducePlanBytes = (size_t)kReduceBatch * (sizeof(ReduceItem) + sizeof(ReduceJoin));
+constexpr size_t reduce_bytes = kReducePlanBytes + (size_t)kReduceBatch * sizeof(ReducePartial);
+
+struct ReduceBatch {
+  std::vector<ReduceItem> items;
+  std::vector<ReduceJoin> joins;
+  std::vector<unsigned char> blob;  // the two as uploaded
+  int parts = 0;
+};
+
+bool rect_valid(const rc2dgi_rect &r, int tw, int th) {  // (in this form nothing overflows)
+  return r.w >= 1 && r.h >= 1 && r.x >= 0 && r.y >= 0 && r.w <= tw - r.x && r.h <= th - r.y;
+}
+
+// Rows of a band of a w x h rectangle, a power of two: a wave gets about 4096 texels (whole passes of 64 / lanes-a-row
+// rows when the rows are narrow, k_reduce_rows; at most 1024 rows), and a rectangle at most kReduceMaxBands bands
+// (only a rectangle of more than 2^22 rows gets taller bands for that).
+int reduce_band_rows(int w, int h) {
+  long long rw = 1;
+  if (w <= kReduceChunk) {
+    int lr = 1;
+    while (lr * kReduceLeaves < w) lr <<= 1;
+    rw = 64 / lr;
+    while (rw * w < 4096 && rw < 1024) rw <<= 1;
+  } else {
+    while (rw * 2 * w <= 4096) rw <<= 1;
+  }
+  while ((h + rw - 1) / rw > kReduceMaxBands) rw <<= 1;
+  return (int)std::min<long long>(rw, 1 << 30);
+}
+
+// one batch: upload its plan in one copy (stream-ordered, after the kernels that read the previous one), two launches
+int reduce_flush(rc2dgi_ctx *c, const TexSource &t, ReduceBatch &b, void *stats_dev) {
+  if (b.items.empty()) return RC2DGI_OK;
+  const int ni = (int)b.items.size(), nj = (int)b.joins.size();
+  // the joins ride behind the items in the host vector and on the device
+  static_assert(alignof(ReduceJoin) == 4 && alignof(ReduceItem) == 4, "a join may follow any number of items");
+  const size_t ibytes = (size_t)ni * sizeof(ReduceItem), jbytes = (size_t)nj * sizeof(ReduceJoin);
+  std::vector<unsigned char> &blob = b.blob;
+  blob.resize(ibytes + jbytes);
+  std::memcpy(blob.data(), b.items.data(), ibytes);
+  if (nj) std::memcpy(blob.data() + ibytes, b.joins.data(), jbytes);
+  ReduceItem *items = reinterpret_cast<ReduceItem *>(c->reduce_buf);
+  ReduceJoin *joins = reinterpret_cast<ReduceJoin *>(c->reduce_buf + ibytes);
+  ReducePartial *parts = reinterpret_cast<ReducePartial *>(c->reduce_buf + kReducePlanBytes);
+  const ReduceInline none{};
+  HIPCHK(c, hipMemcpyAsync(c->reduce_buf, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, launch_reduce_rows(t, none, items, ni, parts, stats_dev, c->stream));
+  if (nj) HIPCHK(c, launch_reduce_bands(none, joins, nj, parts, stats_dev, c->stream));
+  return RC2DGI_OK;
+}
+
+// n >= 1 rectangles of t into the device records stats_dev, enqueued on the context stream.  The scratch is one
+// batch's, however long the list and however tall a rectangle: a full batch is launched and the next one planned.
+int reduce_enqueue(rc2dgi_ctx *c, const TexSource &t, const rc2dgi_rect *rects, int n, void *stats_dev) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->reduce_buf) HIPCHK(c, alloc(&c->reduce_buf, reduce_bytes));
+  ReducePartial *parts = reinterpret_cast<ReducePartial *>(c->reduce_buf + kReducePlanBytes);
+  if (n <= kReduceInline) {  // the plan fits the kernels' arguments: no upload
+    ReduceInline inl{};
+    inl.n = n;
+    int items = 0, nparts = 0;
+    for (int k = 0; k < n; ++k) {
+      const rc2dgi_rect &r = rects[k];
+      ReduceDesc &d = inl.d[k];
+      d = ReduceDesc{0, 0, 0, 0, 1, items, nparts, k};
+      int nb = 1;
+      if (rect_valid(r, t.nx, t.ny)) {
+        const int rw = reduce_band_rows(r.w, r.h);
+        nb = (int)(((long long)r.h + rw - 1) / rw);
+        d = ReduceDesc{r.x, r.y, r.w, r.h, rw, items, nparts, k};
+      }
+      items += nb;
+      if (nb > 1) nparts += nb;
+    }
+    HIPCHK(c, launch_reduce_rows(t, inl, nullptr, items, parts, stats_dev, c->stream));
+    if (nparts) HIPCHK(c, launch_reduce_bands(inl, nullptr, n, parts, stats_dev, c->stream));
+    return RC2DGI_OK;
+  }
+  // One batch of host vectors, planned again after each flush: the copy of a flush has consumed them when it returns
+  // (pageable memory, as paint_prims relies on for its vectors), so host memory is one batch's too.
+  ReduceBatch b;
+  for (int k = 0; k < n; ++k) {
+    const rc2dgi_rect &r = rects[k];
+    const bool ok = rect_valid(r, t.nx, t.ny);
+    const int rw = ok ? reduce_band_rows(r.w, r.h) : 1;
+    const int nb = ok ? (int)(((long long)r.h + rw - 1) / rw) : 1;
+    if (b.items.size() + (size_t)nb > (size_t)kReduceBatch) {
+      if (int rc = reduce_flush(c, t, b, stats_dev)) return rc;
+      b.items.clear();
+      b.joins.clear();
+      b.parts = 0;
+    }
+    if (!ok) {
+      b.items.push_back(ReduceItem{0, 0, 0, 0, 0, (unsigned)k | kReduceFinal});
+    } else if (nb == 1) {
+      b.items.push_back(ReduceItem{r.x, r.y, r.w, 0, r.h, (unsigned)k | kReduceFinal});
+    } else {
+      b.joins.push_back(ReduceJoin{b.parts, nb, k, r.w * r.h});
+      for (int i = 0; i < nb; ++i)
+        b.items.push_back(ReduceItem{r.x, r.y, r.w, i * rw, (int)std::min<long long>((long long)(i + 1) * rw, r.h),
+                                     (unsigned)b.parts++});
+    }
+  }
+  return reduce_flush(c, t, b, stats_dev);
+}
+
+// the checks the two calls share; n == 0 is left to the caller (a successful no-op)
+int reduce_args(rc2dgi_ctx *c, int which, const rc2dgi_rect *rects, int n, const void *stats, TexSource &t) {
+  if (!c) return RC2DGI_E_ARG;
+  RC2DGI_USABLE(c);
+  if (n < 0 || n > kReduceMax) return fail(c, RC2DGI_E_ARG, "reduce: n is 0 .. 1 << 20");
+  if (n > 0 && (!rects || !stats)) return fail(c, RC2DGI_E_ARG, "reduce: null argument");
+  if (int rc = resolve_texture(c, which, RC2DGI_FILTER_POINT, "reduce: ", t)) return rc;
+  if (c->world > 1)
+    return fail(c, RC2DGI_E_UNSUPPORTED, "a row-strip shard's textures hold windows and bands: reduce on an unsharded context");
+  return RC2DGI_OK;
+}
 
 // Validate the call and resolve every view to source pointer, pitch, axes, storage kind and filter, as
 // rc2dgi_download reads that texture.  Views that miss the window are dropped.
@@ -245,6 +373,30 @@ int rc2dgi_raycast(rc2dgi_ctx *c, const rc2dgi_ray *rays, int n, rc2dgi_rayhit *
   if (n == 0) return RC2DGI_OK;
   return query_host(c, rays, (size_t)n * sizeof(rc2dgi_ray), hits, (size_t)n * sizeof(rc2dgi_rayhit),
                     [&](void *in, void *out) { return launch_raycast(s, in, n, out, c->stream); });
+}
+
+// ---- region statistics (rc2dgi_reduce.hip)
+int rc2dgi_reduce_device(rc2dgi_ctx *c, int which, const rc2dgi_rect *rects, int n, void *stats_dev) {
+  TexSource t{};
+  if (int rc = reduce_args(c, which, rects, n, stats_dev, t)) return rc;
+  if (n == 0) return RC2DGI_OK;
+  if (!aligned_to(stats_dev, 8)) return fail(c, RC2DGI_E_ARG, "reduce: the records are aligned to 8 bytes");
+  return reduce_enqueue(c, t, rects, n, stats_dev);
+}
+
+int rc2dgi_reduce(rc2dgi_ctx *c, int which, const rc2dgi_rect *rects, int n, rc2dgi_stats *stats) {
+  TexSource t{};
+  if (int rc = reduce_args(c, which, rects, n, stats, t)) return rc;
+  if (n == 0) return RC2DGI_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = check_chain(c)) return rc;
+  const size_t bytes = (size_t)n * sizeof(rc2dgi_stats);
+  if (int rc = query_buffer(c, c->query_out, c->query_out_cap, bytes)) return rc;
+  if (int rc = reduce_enqueue(c, t, rects, n, c->query_out)) return rc;
+  HIPCHK(c, hipMemcpyAsync(stats, c->query_out, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RC2DGI_OK;
 }
 
 }  // extern "C"

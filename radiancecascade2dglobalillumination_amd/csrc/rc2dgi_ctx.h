@@ -1,6 +1,6 @@
 // rc2dgi_ctx.h -- the context behind the C ABI (include/rc2dgi.h) and the helpers its host units share:
 // rc2dgi_buffers.cpp (sizes, allocation, tables), rc2dgi_frame.cpp (the frame), rc2dgi_group.cpp (RCCL, sharded
-// groups), rc2dgi_autotune.cpp, rc2dgi_compose.cpp (the display frame and the queries) and rc2dgi_capi.cpp (everything
+// groups), rc2dgi_autotune.cpp, rc2dgi_compose.cpp (the display frame, the queries and the region statistics) and rc2dgi_capi.cpp (everything
 // else of the ABI).
 #pragma once
 #include "../../include/rc2dgi.h"
@@ -23,6 +23,7 @@
 #include "rc2dgi_paint.h"
 #include "rc2dgi_present.h"
 #include "rc2dgi_query.h"
+#include "rc2dgi_reduce.h"
 #include "rc2dgi_shard.h"
 #include "rc2dgi_tuning.h"
 
@@ -118,6 +119,8 @@ struct rc2dgi_ctx : rc2dgi::Tuning {
   size_t present_cap = 0;
   unsigned char *query_in = nullptr, *query_out = nullptr;  // rc2dgi_sample / rc2dgi_raycast's points or rays and
   size_t query_in_cap = 0, query_out_cap = 0;               // their results, grown on demand
+  unsigned char *reduce_buf = nullptr;  // rc2dgi_reduce's plan (work items, joins) and band partials of one batch: a
+                                        // fixed size (reduce_bytes, rc2dgi_compose.cpp), allocated at the first call
   int rank = 0, world = 1;
   int ow0 = 0, ow1 = 0;  // screen rows tempRT / the merged colorRT hold (their row 0 = row ow0): [0, H), or a row-strip
                          // shard's own rows (out_buffers)

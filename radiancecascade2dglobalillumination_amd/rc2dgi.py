@@ -97,6 +97,52 @@ def hit_floats(hits):
     return hits[:, HIT_INT_FIELDS:].view(torch.float32)
 
 
+class Rect(ctypes.Structure):
+    """rc2dgi_rect: w x h texels of a render texture from (x, y), GL order (row 0 = the bottom)."""
+    _fields_ = [("x", ctypes.c_int), ("y", ctypes.c_int), ("w", ctypes.c_int), ("h", ctypes.c_int)]
+
+
+class Stats(ctypes.Structure):
+    """rc2dgi_stats: what rc2dgi_reduce reports for one rectangle -- status (STATS_*), texels = w * h and per channel
+    r, g, b, a the count of NaN / infinite values, min and max of the finite ones and their float64 sum in the header's
+    fixed order.  sum[c] / (texels - nonfinite[c]) is the mean."""
+    _fields_ = [("status", ctypes.c_int), ("texels", ctypes.c_int), ("nonfinite", ctypes.c_int * 4),
+                ("min", ctypes.c_float * 4), ("max", ctypes.c_float * 4), ("sum", ctypes.c_double * 4)]
+
+
+STATS_OK, STATS_INVALID = 0, -1
+RECT_DTYPE = np.dtype([(n, np.int32) for n, _ in Rect._fields_])
+STATS_DTYPE = np.dtype([("status", np.int32), ("texels", np.int32), ("nonfinite", np.int32, (4,)),
+                        ("min", np.float32, (4,)), ("max", np.float32, (4,)), ("sum", np.float64, (4,))])
+STATS_WORDS = 22  # an rc2dgi_stats record as int32 words: 6 ints, 8 floats from word 6, 4 doubles from word 14
+REDUCE_MAX = 1 << 20
+
+
+def stats_view(words):
+    """The float and double fields of the int32 (n, 22) tensor RC2DGI.reduce_into fills, from its numpy copy
+    (`words`: that tensor, or an int32 (n, 22) array): a structured STATS_DTYPE array of n records over a copy of
+    the same bytes."""
+    if hasattr(words, "data_ptr"):
+        words = words.cpu().numpy()
+    a = np.ascontiguousarray(words, np.int32)
+    if a.ndim != 2 or a.shape[1] != STATS_WORDS:
+        raise ValueError(f"stats_view: expected (n, {STATS_WORDS}) int32 words, got {a.shape}")
+    return a.reshape(-1).view(STATS_DTYPE)
+
+
+def _rect_array(rects):
+    """rects as a contiguous RECT_DTYPE array: an (n, 4) int array (x, y, w, h) or a RECT_DTYPE array."""
+    a = np.asarray(rects)
+    if a.dtype == RECT_DTYPE:
+        return np.ascontiguousarray(a).reshape(-1)
+    if a.size == 0:  # an empty list: n == 0, a successful no-op of the ABI
+        return np.zeros(0, RECT_DTYPE)
+    a = np.ascontiguousarray(a, np.int32)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError(f"reduce: expected (n, 4) rectangles, got {a.shape}")
+    return a.reshape(-1).view(RECT_DTYPE)
+
+
 def _view_array(views):
     arr = (View * max(len(views), 1))()
     for k, v in enumerate(views):
@@ -180,6 +226,8 @@ def load_library(path: Optional[str] = None):
         "rc2dgi_sample_device": ([vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp], ctypes.c_int),
         "rc2dgi_raycast": ([vp, vp, ctypes.c_int, vp], ctypes.c_int),
         "rc2dgi_raycast_device": ([vp, vp, ctypes.c_int, vp], ctypes.c_int),
+        "rc2dgi_reduce": ([vp, ctypes.c_int, vp, ctypes.c_int, vp], ctypes.c_int),
+        "rc2dgi_reduce_device": ([vp, ctypes.c_int, vp, ctypes.c_int, vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -469,6 +517,46 @@ class RC2DGI:
                                            out.ctypes.data_as(ctypes.c_void_p)), "raycast")
         return out
 
+    # ---------------------------------------------------------------- region statistics
+    def texture_size(self, which):
+        """(width, height) of a render texture: the screen, or the cascade resolution for GI1 / GI2 / BLUR / FINAL_GI."""
+        w = RT[which] if isinstance(which, str) else int(which)
+        if w in (RT["gi1"], RT["gi2"], RT["blur"], RT["final_gi"]):
+            return self.query()[:2]
+        return self.screen_width, self.screen_height
+
+    def reduce(self, which, rects=None):
+        """Per rectangle and channel the count of non-finite values, min and max of the finite ones and their float64
+        sum in the header's fixed order (rc2dgi_reduce): which -- a name of RT or an rc2dgi_rt id; rects -- an (n, 4)
+        int array (x, y, w, h) in texels of that texture, GL order (row 0 = the bottom), or a RECT_DTYPE array; None:
+        the whole texture.  Returns a structured STATS_DTYPE array of n records, synchronously; a rectangle that does
+        not lie inside the texture has status STATS_INVALID and zeros."""
+        w = RT[which] if isinstance(which, str) else int(which)
+        if rects is None:
+            tw, th = self.texture_size(w)
+            rects = [[0, 0, tw, th]]
+        a = _rect_array(rects)
+        out = np.zeros(a.shape[0], STATS_DTYPE)
+        self._check(self._L.rc2dgi_reduce(self._h, w, a.ctypes.data_as(ctypes.c_void_p), a.shape[0],
+                                          out.ctypes.data_as(ctypes.c_void_p)), "reduce")
+        return out
+
+    def reduce_into(self, dst, which, rects) -> None:
+        """The same records into device memory, enqueued on the context stream after whatever frame is in flight
+        (rc2dgi_reduce_device; sync() or order the stream before reading, as with compose_into).  dst: a contiguous
+        int32 (n, 22) torch tensor on this context's GPU, one rc2dgi_stats record of 88 bytes a row (stats_view reads
+        its numpy copy); rects: host memory, as for reduce."""
+        if not getattr(dst, "is_cuda", False) or dst.device.index != self.device:
+            raise TypeError("reduce_into: expected a tensor on this context's GPU")
+        if str(dst.dtype) != "torch.int32" or not dst.is_contiguous():
+            raise TypeError("reduce_into: expected a contiguous int32 tensor")
+        a = _rect_array(rects)
+        if dst.dim() != 2 or dst.shape[1] != STATS_WORDS or dst.shape[0] != a.shape[0]:
+            raise ValueError(f"reduce_into: expected shape ({a.shape[0]}, {STATS_WORDS}), got {tuple(dst.shape)}")
+        w = RT[which] if isinstance(which, str) else int(which)
+        self._check(self._L.rc2dgi_reduce_device(self._h, w, a.ctypes.data_as(ctypes.c_void_p), a.shape[0],
+                                                 ctypes.c_void_p(dst.data_ptr())), "reduce_into")
+
     def set_tuning(self, key: str, value: int) -> None:
         """Performance knobs (results are identical for every value), e.g. rc_variant."""
         self._check(self._L.rc2dgi_set_tuning(self._h, key.encode(), int(value)), f"set_tuning {key}")
@@ -686,4 +774,5 @@ __all__ = ["RC2DGI", "RC2DGIError", "load_library", "abi_version", "RT", "PASS_N
            "plan_rows", "plan_jfa_exchange", "plan_jfa_window", "PLAN_JFA", "PLAN_LEVEL", "PLAN_BLUR", "PLAN_MERGE",
            "View", "display_layout", "FILTER_RT", "FILTER_POINT", "FILTER_LINEAR", "MAX_VIEWS", "Ray", "RayHit",
            "RAY_DTYPE", "HIT_DTYPE", "hit_floats", "RAY_INVALID", "RAY_RANGE", "RAY_EDGE", "RAY_EMISSIVE", "RAY_SURFACE",
-           "RAY_STEPS"]
+           "RAY_STEPS", "Rect", "Stats", "RECT_DTYPE", "STATS_DTYPE", "stats_view", "STATS_OK", "STATS_INVALID",
+           "STATS_WORDS", "REDUCE_MAX"]

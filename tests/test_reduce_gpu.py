@@ -1,0 +1,465 @@
+"""GPU: rectangles of a render texture measured on the device (rc2dgi_reduce / rc2dgi_reduce_device, include/rc2dgi.h)
+against tests/reduce_ref.c, the header's semantics restated in C over the `download` of the same texture.  Every
+comparison is exact equality of bits: status, texels, the counts, min, max and the float64 sums."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from test_reduce_cpu import INT_MAX, build_reduce_ref, gpu_texture, ref_reduce
+
+pytestmark = pytest.mark.gpu
+
+f32 = np.float32
+STORAGES = ["f32", "f16", "rgba8"]
+ALL_RTS = ["color", "emissive", "jump1", "jump2", "dist", "gi1", "gi2", "temp", "blur", "final_gi"]
+CASCADE_RTS = ("gi1", "gi2", "blur", "final_gi")
+E_ARG, E_UNSUPPORTED, E_DEVICE = -1, -5, -7
+EDGES = [255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2047, 2048, 2051]
+
+
+@pytest.fixture(scope="module")
+def R():
+    import torch
+
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    from radiancecascade2dglobalillumination_amd import rc2dgi
+
+    return rc2dgi
+
+
+@pytest.fixture(scope="module")
+def ref_lib(tmp_path_factory):
+    return build_reduce_ref(tmp_path_factory)
+
+
+def same(got, want, what, rects=None):
+    """two arrays of records hold the same bytes (NaNs and signed zeros compare as their bits)"""
+    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.shape, want.shape)
+    g = np.ascontiguousarray(got).view(np.uint32).reshape(len(got), -1)
+    w = np.ascontiguousarray(want).view(np.uint32).reshape(len(want), -1)
+    bad = np.argwhere((g != w).any(1)).reshape(-1)
+    if len(bad):
+        k = int(bad[0])
+        where = "" if rects is None else f" rectangle {np.asarray(rects).reshape(-1, 4)[k].tolist()}"
+        raise AssertionError(f"{what}: {len(bad)} of {len(got)} records differ, first {k}{where}:\n got  {got[k]}\n want {want[k]}")
+
+
+def tex_size(ctx, name):
+    return ctx.cascade_resolution if name in CASCADE_RTS else (ctx.screen_width, ctx.screen_height)
+
+
+def demo_context(R, W, H, N, rs, storage, frame=True):
+    from radiancecascade2dglobalillumination_amd import scenes
+
+    ctx = R.RC2DGI(W, H, cascade_count=N, render_scale=rs, storage=storage)
+    color, emis = scenes.demo(W, H)
+    ctx.upload("color", color)
+    ctx.upload("emissive", emis)
+    if frame:
+        ctx.do_rc2dgi()
+        ctx.sync()
+    return ctx, color, emis
+
+
+def check(ctx, ref_lib, name, rects, what, tex=None):
+    """reduce(name, rects) equals the reference over the download of that texture; returns the records"""
+    tex = ctx.download(name) if tex is None else tex
+    got = ctx.reduce(name, rects)
+    same(got, ref_reduce(ref_lib, tex, rects), what, rects)
+    return got
+
+
+# ------------------------------------------------------------------ 1: the decode of every texture and storage
+@pytest.fixture(scope="module", params=STORAGES)
+def small(R, request):
+    ctx, _, _ = demo_context(R, 96, 80, 2, 0.5, request.param)
+    assert ctx.cascade_resolution == (48, 40)
+    yield ctx
+    ctx.close()
+
+
+@pytest.mark.parametrize("name", ALL_RTS)
+def test_whole_texture_and_single_texels_are_the_download(R, ref_lib, small, name):
+    nx, ny = tex_size(small, name)
+    tex = small.download(name)
+    whole = small.reduce(name)  # rects=None: the whole texture
+    same(whole, ref_reduce(ref_lib, tex, [[0, 0, nx, ny]]), f"{small.storage} {name} whole")
+    assert whole["texels"][0] == nx * ny and whole["status"][0] == 0
+    # 1 x 1 rectangles: every texel of a cascade texture, a 16 x 16 corner of a screen texture
+    cx, cy = (nx, ny) if name in CASCADE_RTS else (16, 16)
+    x0, y0 = nx - cx, ny - cy  # the top right corner
+    ys, xs = np.mgrid[y0:ny, x0:nx]
+    rects = np.stack([xs.ravel(), ys.ravel(), np.ones(cx * cy, int), np.ones(cx * cy, int)], 1)
+    got = check(small, ref_lib, name, rects, f"{small.storage} {name} 1 x 1", tex)
+    texel = tex[y0:ny, x0:nx].reshape(-1, 4) + f32(0.0)
+    assert np.isfinite(texel).all()
+    assert np.array_equal(got["min"].view(np.uint32), texel.view(np.uint32))
+    assert np.array_equal(got["max"].view(np.uint32), texel.view(np.uint32))
+    assert np.array_equal(got["sum"], texel.astype(np.float64)) and not got["nonfinite"].any()
+    # and equals a POINT sample at the texel's centre
+    uv = np.stack([(xs.ravel() + f32(0.5)) / f32(nx), (ys.ravel() + f32(0.5)) / f32(ny)], 1).astype(f32)
+    assert np.array_equal(small.sample(name, uv, 1).view(np.uint32), tex[y0:ny, x0:nx].reshape(-1, 4).view(np.uint32))
+
+
+@pytest.mark.parametrize("storage", STORAGES)
+def test_color_before_a_frame_is_the_input(R, ref_lib, storage):
+    ctx, color, _ = demo_context(R, 96, 80, 2, 0.5, storage, frame=False)
+    rects = [[0, 0, 96, 80], [5, 7, 40, 33], [95, 79, 1, 1]]
+    painted = ctx.download("color")
+    assert painted.any() and np.allclose(painted, color, atol=1e-6)
+    before = check(ctx, ref_lib, "color", rects, storage + " before the frame", painted)
+    ctx.do_rc2dgi()
+    ctx.sync()
+    after = check(ctx, ref_lib, "color", rects, storage + " after the frame")
+    assert not np.array_equal(before["sum"], after["sum"])
+    ctx.close()
+
+
+@pytest.mark.parametrize("storage", STORAGES)
+def test_gi2_with_one_cascade_is_constant(R, ref_lib, storage):
+    ctx, _, _ = demo_context(R, 96, 80, 1, 0.5, storage)
+    cw, ch = ctx.cascade_resolution
+    rects = [[0, 0, cw, ch], [3, 2, 7, 5], [cw - 1, ch - 1, 1, 1]]
+    got = ctx.reduce("gi2", rects)
+    for k, (x, y, w, h) in enumerate(rects):
+        assert got["status"][k] == 0 and got["texels"][k] == w * h and not got["nonfinite"][k].any()
+        assert got["min"][k].tolist() == [0, 0, 0, 1] and got["max"][k].tolist() == [0, 0, 0, 1]
+        assert got["sum"][k].tolist() == [0, 0, 0, w * h]
+    check(ctx, ref_lib, "gi2", rects, storage)
+    ctx.close()
+
+
+# ------------------------------------------------------------------ 2: tree widths and heights
+def wild_context(R, W, H, specials=True):
+    """f32, one cascade, no frame: COLOR is the uploaded values of the CPU tests' generator, with its specials"""
+    ctx = R.RC2DGI(W, H, cascade_count=1, storage="f32")
+    v = gpu_texture(W, H, specials)  # (tests/test_reduce_cpu.py asserts that the all-finite ones tell the orders apart)
+    ctx.upload("color", v)
+    tex = ctx.download("color")
+    bits = tex.view(np.uint32)
+    assert np.array_equal(bits, v.view(np.uint32)), "an f32 upload is stored as it is"
+    if specials:
+        assert np.isnan(tex).any() and np.isinf(tex).any() and (bits == 0x80000000).any() and (bits == 0x7F7FFFFF).any()
+        assert ((bits & 0x7F800000) == 0).any() and (bits == 1).any(), "subnormals reach the texture"
+    return ctx, tex
+
+
+@pytest.fixture(scope="module")
+def wide(R):
+    ctx, tex = wild_context(R, 2051, 9)
+    yield ctx, tex
+    ctx.close()
+
+
+@pytest.fixture(scope="module")
+def tall(R):
+    ctx, tex = wild_context(R, 9, 2051)
+    yield ctx, tex
+    ctx.close()
+
+
+def test_every_width_to_130_at_unaligned_origins(R, ref_lib, wide):
+    ctx, tex = wide
+    rng = np.random.default_rng(11)
+    rects = []
+    for w in range(1, 131):
+        for _ in range(3):
+            h = int(rng.integers(1, 10))
+            rects.append([int(rng.integers(0, 2051 - w + 1)), int(rng.integers(0, 9 - h + 1)), w, h])
+        rects.append([int(rng.integers(0, (2051 - w) // 2)) * 2 + 1, 0, w, 9])  # an odd x
+    got = check(ctx, ref_lib, "color", rects, "widths 1 .. 130", tex)
+    assert got["nonfinite"].any() and (got["status"] == 0).all()
+
+
+def test_every_height_to_130_at_unaligned_origins(R, ref_lib, tall):
+    ctx, tex = tall
+    rng = np.random.default_rng(12)
+    rects = []
+    for h in range(1, 131):
+        for _ in range(3):
+            w = int(rng.integers(1, 10))
+            rects.append([int(rng.integers(0, 9 - w + 1)), int(rng.integers(0, 2051 - h + 1)), w, h])
+        rects.append([0, int(rng.integers(0, (2051 - h) // 2)) * 2 + 1, 9, h])  # an odd y
+    got = check(ctx, ref_lib, "color", rects, "heights 1 .. 130", tex)
+    assert got["nonfinite"].any() and (got["status"] == 0).all()
+
+
+def test_widths_around_the_powers_of_two(R, ref_lib, wide):
+    """Full height.  A work item of k_reduce_rows is whole rows of any width, walked in chunks of 256 leaves, and at
+    most 1024 rows (reduce_band_rows): 2051 = 2 * 1024 + 3 spans two such blocks plus 3 either way, so the screens
+    are not enlarged."""
+    ctx, tex = wide
+    rng = np.random.default_rng(13)
+    rects = []
+    for w in EDGES:
+        rects.append([0, 0, w, 9])
+        rects.append([2051 - w, 0, w, 9])
+        if w < 2051:
+            rects.append([int(rng.integers(0, 2051 - w + 1)), 0, w, 9])
+        rects.append([int(rng.integers(0, 2051 - w + 1)), 2, w, 5])
+    check(ctx, ref_lib, "color", rects, "wide rectangles", tex)
+
+
+def test_heights_around_the_powers_of_two(R, ref_lib, tall):
+    ctx, tex = tall
+    rng = np.random.default_rng(14)
+    rects = []
+    for h in EDGES:
+        rects.append([0, 0, 9, h])
+        rects.append([0, 2051 - h, 9, h])
+        for w in (1, 2, 3, 5, 8):
+            rects.append([int(rng.integers(0, 9 - w + 1)), int(rng.integers(0, 2051 - h + 1)), w, h])
+    check(ctx, ref_lib, "color", rects, "tall rectangles", tex)
+
+
+def test_all_finite_data_in_the_same_order(R, ref_lib):
+    """The generator without its specials: a step of k_reduce_rows whose 1024 values are all finite takes a form
+    without selects, which the textures above (ten specials a step) never reach on wide rows."""
+    ctx, tex = wild_context(R, 2051, 9, specials=False)
+    rng = np.random.default_rng(15)
+    rects = [[0, 0, 2051, 9], [0, 0, 2048, 9], [3, 0, 2048, 8], [1, 1, 1024, 7], [5, 2, 1025, 4], [7, 0, 257, 9]]
+    rects += [[int(rng.integers(0, 2051 - w + 1)), 0, w, 9] for w in EDGES]
+    rects += [[int(rng.integers(0, 1900)), int(rng.integers(0, 5)), int(rng.integers(1, 131)), int(rng.integers(1, 5))]
+              for _ in range(200)]
+    got = check(ctx, ref_lib, "color", rects, "finite values", tex)
+    assert not got["nonfinite"].any()
+    ctx.close()
+
+
+def test_all_finite_heights_in_the_same_order(R, ref_lib):
+    ctx, tex = wild_context(R, 9, 2051, specials=False)
+    rng = np.random.default_rng(16)
+    rects = [[0, 0, 9, h] for h in EDGES] + [[2, 2051 - h, 5, h] for h in EDGES]
+    rects += [[int(rng.integers(0, 5)), int(rng.integers(0, 1900)), int(rng.integers(1, 5)), int(rng.integers(1, 131))]
+              for _ in range(200)]
+    check(ctx, ref_lib, "color", rects, "finite values, tall", tex)
+    ctx.close()
+
+
+BIG_RECTS = [[0, 0, 2051, 1030], [3, 1, 2048, 1029], [1, 0, 2049, 513], [2, 3, 2050, 512], [0, 7, 2051, 511],
+             [700, 5, 1025, 193], [2, 3, 1024, 129], [9, 0, 129, 200], [11, 7, 128, 150], [0, 0, 2051, 1],
+             [5, 1029, 300, 1], [4, 2, 257, 1028]]
+
+
+@pytest.fixture(scope="module", params=[True, False], ids=["specials", "finite"])
+def big(R, request):
+    ctx, tex = wild_context(R, 2051, 1030, specials=request.param)
+    yield ctx, tex
+    ctx.close()
+
+
+def test_wide_and_tall_at_once(R, ref_lib, big):
+    """Rows of more than one chunk in bands of one or two rows.  The second launch takes 512 band partials a step: the
+    rectangles have 1030 (two steps and 6), 515, 513, 512, 511 and fewer bands."""
+    ctx, tex = big
+    check(ctx, ref_lib, "color", BIG_RECTS, "2051 x 1030", tex)
+
+
+# ------------------------------------------------------------------ 2b: lists longer than one batch of work items
+BATCH = 1 << 16  # kReduceBatch (csrc/rc2dgi_reduce.h): work items, and band partials, of one pair of launches
+
+
+def both_variants(R, ctx, rects, want, what):
+    """the host variant, and the device variant into a poisoned tensor, equal `want`"""
+    import torch
+
+    same(ctx.reduce("color", rects), want, what + ", host variant", rects)
+    dst = torch.full((len(rects), 22), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    ctx.reduce_into(dst, "color", rects)
+    ctx.sync()
+    same(R.stats_view(dst), want, what + ", device variant", rects)
+
+
+def test_tall_rectangles_across_a_batch_boundary(R, ref_lib, big):
+    """176 rectangles of 511 to 1030 bands each: 136 000 work items, three batches over the same plan buffer and the
+    same partials, whose indices restart at 0 in each.  No rectangle ends on a boundary, so one straddles each and goes
+    whole into the next batch.  Each distinct rectangle is referenced once."""
+    ctx, tex = big
+    distinct = np.int32(BIG_RECTS[:5] + [[1, 1, 2050, 1029], [0, 0, 2051, 1029], [2, 0, 2049, 1030]])
+    bands = [1030, 515, 513, 512, 511, 1029, 1029, 1030]  # rows a band: 1 for w > 2048, 2 for 2048
+    order = np.tile(np.arange(8), 22)
+    items = np.cumsum(np.array(bands)[order])
+    assert items[-1] > 2 * BATCH and not np.isin([BATCH, 2 * BATCH], items).any(), "a rectangle straddles each boundary"
+    want = ref_reduce(ref_lib, tex, distinct)[order]
+    both_variants(R, ctx, distinct[order], want, "tall rectangles over three batches")
+
+
+def test_sprites_across_a_batch_boundary(R, ref_lib, big):
+    """150 000 rectangles of one band each, 5 % of them invalid: three batches, the last one short."""
+    ctx, tex = big
+    rects, bad = sprite_rects(150000, 2051, 1030, 23)
+    assert len(rects) > 2 * BATCH and len(bad) > 6000
+    want = ref_reduce(ref_lib, tex, rects)
+    assert (want["status"][bad] == -1).all() and (want["status"] == 0).sum() == len(rects) - len(bad)
+    both_variants(R, ctx, rects, want, "sprites over three batches")
+
+
+# ------------------------------------------------------------------ 3: many small rectangles
+def sprite_rects(n, tw, th, seed):
+    """n random rectangles with w, h in 1 .. 40 inside tw x th, 5 % of them invalid in one of the ways there are"""
+    rng = np.random.default_rng(seed)
+    w, h = rng.integers(1, 41, n), rng.integers(1, 41, n)
+    x, y = (rng.random(n) * (tw - w + 1)).astype(int), (rng.random(n) * (th - h + 1)).astype(int)
+    r = np.stack([x, y, w, h], 1).astype(np.int64)
+    bad = np.flatnonzero(rng.random(n) < 0.05)
+    for k in bad:
+        kind = int(rng.integers(0, 8))
+        if kind == 0: r[k, 2] = 0
+        elif kind == 1: r[k, 3] = 0
+        elif kind == 2: r[k, 2] = -int(rng.integers(1, 50))
+        elif kind == 3: r[k, 3] = -INT_MAX - 1
+        elif kind == 4: r[k, int(rng.integers(0, 2))] = -1
+        elif kind == 5: r[k, 0] = tw - r[k, 2] + 1          # one texel over the right edge
+        elif kind == 6: r[k, 1] = th - r[k, 3] + 1          # one texel over the top edge
+        else: r[k, int(rng.integers(0, 2))] = INT_MAX
+    return r.astype(np.int32), bad
+
+
+@pytest.fixture(scope="module", params=STORAGES)
+def sprites_ctx(R, request):
+    ctx, _, _ = demo_context(R, 200, 160, 3, 1.0, request.param)
+    yield ctx
+    ctx.close()
+
+
+def test_twenty_thousand_sprites(R, ref_lib, sprites_ctx):
+    ctx = sprites_ctx
+    tw, th = ctx.cascade_resolution
+    assert tw >= 41 and th >= 41
+    rects, bad = sprite_rects(20000, tw, th, 21)
+    assert 800 < len(bad) < 1200
+    got = check(ctx, ref_lib, "final_gi", rects, f"{ctx.storage} sprites")
+    zero = np.zeros(1, R.STATS_DTYPE)
+    zero["status"] = -1
+    assert (got["status"][bad] == -1).all() and all(got[k].tobytes() == zero[0].tobytes() for k in bad)
+    ok = np.setdiff1d(np.arange(20000), bad)
+    assert (got["status"][ok] == 0).all() and np.array_equal(got["texels"][ok], rects[ok, 2] * rects[ok, 3])
+    assert got["sum"][ok, :3].any() and not got["nonfinite"].any()
+
+
+# ------------------------------------------------------------------ 4: the device variant
+@pytest.mark.parametrize("storage", STORAGES)
+def test_device_variant_after_an_enqueued_frame(R, ref_lib, storage):
+    import torch
+
+    ctx, _, _ = demo_context(R, 200, 160, 3, 1.0, storage)
+    tw, th = ctx.cascade_resolution
+    rects, _ = sprite_rects(500, tw, th, 22)
+    rects = np.concatenate([rects, np.int32([[0, 0, tw, th]])])
+    n = len(rects)
+    ctx.set_shader_value("_SunAngle", 1.25)  # the next frame differs from the one already there
+    old = ctx.reduce("final_gi", rects)
+    # carved out of a poisoned buffer, 8 bytes off a 16-byte boundary: the loosest alignment the ABI admits
+    raw = torch.full((2 + n * 22 + 6,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+    dst = raw[2:2 + n * 22].view(n, 22)
+    assert dst.data_ptr() % 16 == 8 and dst.is_contiguous()
+    torch.cuda.synchronize()
+    ctx.do_rc2dgi()
+    ctx.reduce_into(dst, "final_gi", rects)  # no sync between the two
+    ctx.sync()
+    words = raw.cpu().numpy()
+    assert (words[:2] == 0x5A5A5A5A).all() and (words[2 + n * 22:] == 0x5A5A5A5A).all(), "bytes outside the records"
+    got = R.stats_view(dst)
+    want = ctx.reduce("final_gi", rects)
+    same(got, want, storage + " device variant against the host variant", rects)
+    same(want, ref_reduce(ref_lib, ctx.download("final_gi"), rects), storage + " host variant", rects)
+    assert not np.array_equal(old["sum"], want["sum"]), "the records are of the new frame"
+    # a destination 4 bytes off alignment; n == 0 with null pointers
+    L, h = ctx._L, ctx._h
+    r = R._rect_array(rects)
+    assert L.rc2dgi_reduce_device(h, 9, r.ctypes.data, n, ctypes.c_void_p(raw.data_ptr() + 4)) == E_ARG
+    assert b"8 bytes" in L.rc2dgi_last_error(h)
+    assert L.rc2dgi_reduce_device(h, 9, None, 0, None) == 0 and L.rc2dgi_reduce(h, 9, None, 0, None) == 0
+    ctx.sync()
+    assert np.array_equal(raw.cpu().numpy(), words), "a refused call wrote"
+    with pytest.raises((TypeError, ValueError)):
+        ctx.reduce_into(dst[:, :11], "final_gi", rects)
+    ctx.close()
+
+
+# ------------------------------------------------------------------ 5: errors
+def test_errors_leave_a_valid_context(R, ref_lib):
+    import torch
+
+    ctx, _, _ = demo_context(R, 96, 80, 3, 0.5, "f32", frame=False)
+    L, h = ctx._L, ctx._h
+    rects = R._rect_array([[0, 0, 48, 40], [3, 5, 17, 9], [47, 39, 1, 1], [40, 0, 9, 1]])
+    n = len(rects)
+    out = np.zeros(n, R.STATS_DTYPE)
+    d_out = torch.zeros((n + 1, 22), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    dp = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + off)  # noqa: E731
+    ctx.do_rc2dgi()
+    ctx.sync()
+    want = ctx.reduce("final_gi", rects)
+    assert want["status"].tolist() == [0, 0, 0, -1]
+
+    def check_code(code, expect):
+        """the call failed as documented, said why, and the context still answers a valid reduction"""
+        assert code == expect, (code, expect)
+        assert L.rc2dgi_last_error(h), "no message"
+        same(ctx.reduce("final_gi", rects), want, "after an error")
+
+    for which in (-1, 10):
+        check_code(L.rc2dgi_reduce(h, which, p(rects), n, p(out)), E_ARG)
+        check_code(L.rc2dgi_reduce_device(h, which, p(rects), n, dp(d_out)), E_ARG)
+    for bad_n in (-1, (1 << 20) + 1):
+        check_code(L.rc2dgi_reduce(h, 9, p(rects), bad_n, p(out)), E_ARG)
+        check_code(L.rc2dgi_reduce_device(h, 9, p(rects), bad_n, dp(d_out)), E_ARG)
+    check_code(L.rc2dgi_reduce(h, 9, None, n, p(out)), E_ARG)
+    check_code(L.rc2dgi_reduce(h, 9, p(rects), n, None), E_ARG)
+    check_code(L.rc2dgi_reduce_device(h, 9, None, n, dp(d_out)), E_ARG)
+    check_code(L.rc2dgi_reduce_device(h, 9, p(rects), n, None), E_ARG)
+    for off in (1, 2, 4, 12):
+        check_code(L.rc2dgi_reduce_device(h, 9, p(rects), n, dp(d_out, off)), E_ARG)
+    assert not out.view(np.uint8).any() and not d_out.cpu().numpy().any(), "a refused call wrote"
+    # what is allowed: n == 0 with null pointers, a destination 8 bytes in
+    assert L.rc2dgi_reduce(h, 9, None, 0, None) == 0 and L.rc2dgi_reduce_device(h, 9, None, 0, None) == 0
+    assert L.rc2dgi_reduce_device(h, 9, p(rects), n, dp(d_out, 8)) == 0
+    ctx.sync()
+    same(R.stats_view(d_out.cpu().numpy().reshape(-1)[2:2 + n * 22].reshape(n, 22)), want, "records 8 bytes in")
+    # a row-strip shard's textures hold windows and bands
+    ctx.set_shard(0, 2)
+    codes = [L.rc2dgi_reduce(h, 9, p(rects), n, p(out)), L.rc2dgi_reduce_device(h, 9, p(rects), n, dp(d_out))]
+    assert codes == [E_UNSUPPORTED] * 2 and b"shard" in L.rc2dgi_last_error(h)
+    with pytest.raises(R.RC2DGIError) as ei:
+        ctx.reduce("final_gi", rects)
+    assert ei.value.code == E_UNSUPPORTED and "shard" in str(ei.value)
+    ctx.set_shard(0, 1)
+    ctx.do_rc2dgi()
+    ctx.sync()
+    same(ctx.reduce("final_gi", rects), want, "after the errors")
+    same(want, ref_reduce(ref_lib, ctx.download("final_gi"), rects.view(np.int32).reshape(-1, 4)), "against the reference")
+    ctx.close()
+
+
+def test_chain_timeout_is_reported_by_the_host_variant(R, ref_lib):
+    """The existing diagnostic knob, as tests/test_query_gpu.py uses it for the queries: rc_chain_spin -1 makes every
+    wait of the chained cascade launch time out at once, the frame's cascades are wrong, and the next synchronising
+    call says so."""
+    from radiancecascade2dglobalillumination_amd import scenes
+
+    W, H, N = 1200, 900, 6
+    color, emis = scenes.demo(W, H)
+    ctx = R.RC2DGI(W, H, cascade_count=N, ray_range=2.0)
+    ctx.frame(color, emis)
+    ctx.sync()
+    cw, ch = ctx.cascade_resolution
+    rects = np.int32([[0, 0, cw, ch], [100, 200, 64, 64], [cw - 33, ch - 17, 33, 17]])
+    want = ctx.reduce("final_gi", rects)
+    ctx.set_tuning("rc_chain", 1)
+    ctx.set_tuning("rc_chain_spin", -1)
+    ctx.do_rc2dgi()
+    with pytest.raises(R.RC2DGIError) as ei:
+        ctx.reduce("final_gi", rects)
+    assert ei.value.code == E_DEVICE and "cascade chain" in str(ei.value)
+    assert ctx.get_tuning("rc_chain") == 0
+    ctx.set_tuning("rc_chain_spin", 0)
+    ctx.do_rc2dgi()
+    got = ctx.reduce("final_gi", rects)
+    same(got, want, "records after the fallback", rects)
+    same(got, ref_reduce(ref_lib, ctx.download("final_gi"), rects), "against the reference", rects)
+    ctx.close()
