@@ -1,7 +1,7 @@
 /* layout.c -- sizeof / offsetof of the ABI structs, as the C compiler lays them out, for
  * tests/test_host_cpu.py to compare with the C# StructLayout(Sequential) mirrors in
  * host/csharp/RC2DGINative.cs (Config, Prim; View: tests/test_present_cpu.py; Ray, RayHit: tests/test_query_cpu.py;
- * Rect, Stats: tests/test_reduce_cpu.py). */
+ * Rect, Stats: tests/test_reduce_cpu.py; Tone: tests/test_tone_cpu.py). */
 #include <stddef.h>
 #include <stdio.h>
 
@@ -72,5 +72,8 @@ int main(void) {
   F(rc2dgi_stats, min);
   F(rc2dgi_stats, max);
   F(rc2dgi_stats, sum);
+  printf("rc2dgi_tone %zu\n", sizeof(rc2dgi_tone));
+  F(rc2dgi_tone, exposure);
+  F(rc2dgi_tone, curve);
   return 0;
 }

@@ -111,6 +111,26 @@ static unsafe class RC2DGINative
     [DllImport(Lib)] public static extern int rc2dgi_reduce(IntPtr ctx, int which, TexRect* rects, int n, Stats* stats);
     [DllImport(Lib)] public static extern int rc2dgi_reduce_device(IntPtr ctx, int which, TexRect* rects, int n, void* statsDev);
 
+    // Edge tables: bin(v) = the number of ascending float edges <= v, exact on any hardware.  With 255 edges a tone
+    // curve (any monotone float -> byte map; the host computes the edges), with m edges a histogram's bin index.
+    // A Tone is a view's exposure and curve slot (0: q8, the untoned conversion; 1 .. 8: rc2dgi_set_curve's tables);
+    // a histogram record is m + 4 uints {status, texels, nan, bin[0] .. bin[m]}.  rects and edges are host memory.
+    public const int CurveEdges = 255, MaxCurves = 8, HistMaxEdges = 1023;
+    public enum Channel { R = 0, G = 1, B = 2, A = 3, Luma = 4 }
+    [StructLayout(LayoutKind.Sequential, Size = 8)]
+    public struct Tone
+    {
+        public float Exposure;         // >= 0, finite: each colour channel is multiplied by it (one float multiply)
+        public int Curve;              // 0: q8; 1 .. MaxCurves: that slot's 255 edges
+    }
+    [DllImport(Lib)] public static extern int rc2dgi_check_edges(float* edges, int m);
+    [DllImport(Lib)] public static extern int rc2dgi_curve_q8(float* edges255);
+    [DllImport(Lib)] public static extern int rc2dgi_set_curve(IntPtr ctx, int slot, float* edges255);
+    [DllImport(Lib)] public static extern int rc2dgi_compose_tone(IntPtr ctx, View* views, Tone* tones, int n, int outW, int outH, byte* clearRgba, void* host, int pitchBytes);
+    [DllImport(Lib)] public static extern int rc2dgi_compose_tone_device(IntPtr ctx, View* views, Tone* tones, int n, int outW, int outH, byte* clearRgba, void* dev, int pitchBytes);
+    [DllImport(Lib)] public static extern int rc2dgi_histogram(IntPtr ctx, int which, int channel, TexRect* rects, int n, float* edges, int m, uint* counts);
+    [DllImport(Lib)] public static extern int rc2dgi_histogram_device(IntPtr ctx, int which, int channel, TexRect* rects, int n, float* edges, int m, void* countsDev);
+
     static IntPtr ctx;
     static Config config;
     static byte[] scratch = Array.Empty<byte>();
@@ -223,6 +243,25 @@ static unsafe class RC2DGINative
             m[c] = finite > 0 ? (float)(st.Sum[c] / finite) : 0f;
         }
         return new System.Numerics.Vector4(m[0], m[1], m[2], m[3]);
+    }
+
+    // Auto-exposure without a Download: the luminance histogram of the final GI over a texture rectangle (256
+    // log-spaced edges from 2^-16 to 2^16), its 90th percentile, and the exposure that maps that luminance to `key`
+    // (0.8: just below white).  Pass the result as the main view's Tone to rc2dgi_compose_tone; Curve names a slot set
+    // with rc2dgi_set_curve (an sRGB table, say), 0 shows the scaled values through q8.
+    public static Tone AutoExposure(TexRect rect, float key, int curve = 0)
+    {
+        const int m = 256;
+        float* edges = stackalloc float[m];
+        for (int i = 0; i < m; ++i) edges[i] = MathF.Pow(2f, -16f + 32f * i / (m - 1));
+        uint* rec = stackalloc uint[m + 4];
+        Check(rc2dgi_histogram(ctx, (int)RT.FinalGI, (int)Channel.Luma, &rect, 1, edges, m, rec), "histogram");
+        long counted = (long)rec[1] - rec[2], run = 0;
+        if (rec[0] != 0 || counted <= 0) return new Tone { Exposure = 1f, Curve = curve };
+        int b = 0;
+        for (; b <= m; ++b) { run += rec[3 + b]; if (run * 10 >= counted * 9) break; }
+        float level = edges[Math.Min(b, m - 1)];   // the edge at which the running count reaches 90 %
+        return new Tone { Exposure = key / level, Curve = curve };
     }
 
     public static Prim Rect(Rectangle r, Color c) => new Prim { Kind = 0, X = r.X, Y = r.Y, W = r.Width, H = r.Height, R = c.R, G = c.G, B = c.B, A = c.A };

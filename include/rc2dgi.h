@@ -62,7 +62,8 @@ typedef enum rc2dgi_status {
   RC2DGI_E_STATE = -6,        /* call not valid in the current state */
   RC2DGI_E_DEVICE = -7        /* a device-side check failed: an enqueued frame's results are wrong (the cascade
                                  chain's wait timed out; reported by the next rc2dgi_sync / _download /
-                                 _download_level / _compose / _reduce / _do / _do_phase) */
+                                 _download_level / _compose / _reduce / _compose_tone / _histogram / _do /
+                                 _do_phase) */
 } rc2dgi_status;
 
 typedef enum rc2dgi_storage {
@@ -342,6 +343,94 @@ typedef struct rc2dgi_stats {
 int rc2dgi_reduce(rc2dgi_ctx *ctx, int which, const rc2dgi_rect *rects, int n, rc2dgi_stats *stats);
 int rc2dgi_reduce_device(rc2dgi_ctx *ctx, int which, const rc2dgi_rect *rects, int n, void *stats_dev);
 
+/* ---- edge tables: tone curves for the views and histograms of rectangles.  (An exposure for the HDR final GI that
+ * rc2dgi_compose clamps into 8 bits: histogram its luminance, take a percentile, show the frame through
+ * rc2dgi_compose_tone with that exposure and an sRGB or filmic curve -- nothing is downloaded.)  Both rest on one
+ * primitive that is exact on any hardware: a table of m ascending float edges e[0] <= e[1] <= .. <= e[m-1] with
+ *
+ *            bin(v) = the number of edges e[i] with e[i] <= v            (0 .. m; IEEE <=, no rounding anywhere)
+ *
+ * With 255 edges bin is a tone curve, any monotone map from a float to a byte: the host computes the edges of sRGB,
+ * gamma, Reinhard or a filmic curve in whatever precision it likes and the device evaluates no transcendental.  With
+ * m edges bin is a histogram's bin index.  A restatement on the host (a linear scan) equals the device bit for bit.
+ *   Edges may repeat (a repeated edge makes a bin that is always empty) and may be +-inf or -0.0; IEEE <= treats -0.0
+ *   and +0.0 alike, so -0.0 >= a +0.0 edge.  A value equal to an edge lands above it.  bin(NaN) is undefined at this
+ *   level: each caller below says what a NaN becomes.
+ * rc2dgi_check_edges (host-only): RC2DGI_OK, or RC2DGI_E_ARG for a null table, m < 1, a NaN edge or e[i] > e[i+1].
+ * rc2dgi_curve_q8 (host-only): the 255 edges with bin(v) == q8(v) = rint(clamp(v, 0, 1) * 255) for every float v that
+ * is no NaN (q8(NaN) = 0 is the callers' NaN rule below): edge k - 1, k = 1 .. 255, is the smallest non-negative float
+ * x with q8(x) >= k, found by bisection over float bit patterns (the bits of a non-negative float order as the float
+ * does) on q8 as rc2dgi_device.h states it.  The table is strictly ascending and edge 127 (k = 128) is exactly 0.5f:
+ * 0.5f * 255 = 127.5 rounds to the even 128. */
+#define RC2DGI_CURVE_EDGES 255
+#define RC2DGI_MAX_CURVES 8
+#define RC2DGI_HIST_MAX_EDGES 1023
+int rc2dgi_check_edges(const float *edges, int m);
+int rc2dgi_curve_q8(float *edges255);
+
+/* ---- toned views: rc2dgi_compose with an exposure and a tone curve per view.
+ * Everything said under rc2dgi_compose holds word for word -- clear, draw order, sampling, texel decode, border,
+ * errors, the refusal on a row-strip shard, the host variant's synchronisation and chain timeout (RC2DGI_E_DEVICE) --
+ * with one step changed.  Where a draw forms its 8-bit source from the sampled float4 (r, g, b, a), view k uses
+ *            (T(r * E), T(g * E), T(b * E), q8(a)),     E = tones[k].exposure, each product ONE fp32 multiply,
+ *   T = q8                               when tones[k].curve == 0,
+ *   T(v) = isnan(v) ? 0 : bin(v)         over the 255 edges of curve slot tones[k].curve otherwise.
+ * Alpha and the border colour are not toned; the blend is unchanged.  tones == NULL, or every record {1.0f, 0}, is
+ * rc2dgi_compose exactly (x * 1.0f is x for every float, a NaN stays one); so is {1.0f, s} with rc2dgi_curve_q8's table
+ * in slot s.  Any render texture in any storage mode may be toned: the value toned is the float rc2dgi_download
+ * returns (DIST at exposure 255 shows which texels have a non-zero low byte, the faintest distances).  0 * inf is NaN
+ * and shows as 0.
+ * rc2dgi_set_curve(ctx, slot, edges255): slot 1 .. RC2DGI_MAX_CURVES; copies the 255 edges into the context during the
+ * call, and from there, ordered on the context stream, into a context-owned device table: a compose enqueued before
+ * the call keeps the old curve, one enqueued after it uses the new one.  edges255 == NULL clears the slot.
+ * Errors, each leaving the context valid: those of rc2dgi_compose; RC2DGI_E_ARG for an exposure that is NaN, infinite
+ * or negative, a curve outside 0 .. RC2DGI_MAX_CURVES, a slot outside 1 .. RC2DGI_MAX_CURVES, a table that
+ * rc2dgi_check_edges refuses; RC2DGI_E_STATE for a view that names a slot that is not set.  These calls only add
+ * exports: RC2DGI_ABI_VERSION stays 5. */
+typedef struct rc2dgi_tone {
+  float exposure;            /* E >= 0, finite */
+  int curve;                 /* 0: q8; 1 .. RC2DGI_MAX_CURVES: that slot's table */
+} rc2dgi_tone;               /* 8 bytes, blittable */
+int rc2dgi_set_curve(rc2dgi_ctx *ctx, int slot, const float *edges255);
+int rc2dgi_compose_tone(rc2dgi_ctx *ctx, const rc2dgi_view *views, const rc2dgi_tone *tones, int n, int out_w, int out_h,
+                        const unsigned char *clear_rgba, void *host, int pitch_bytes);
+int rc2dgi_compose_tone_device(rc2dgi_ctx *ctx, const rc2dgi_view *views, const rc2dgi_tone *tones, int n, int out_w,
+                               int out_h, const unsigned char *clear_rgba, void *dev, int pitch_bytes);
+
+/* ---- histograms of rectangles: for each of n rectangles of a render texture, how many of its texels fall into each
+ * bin of an edge table.
+ *   which, texels, rect   exactly as for rc2dgi_reduce: any rc2dgi_rt, a texel's value is what rc2dgi_download returns,
+ *            a rectangle is valid when w >= 1, h >= 1, x >= 0, y >= 0, w <= TW - x and h <= TH - y (compared in this
+ *            form), with no wrap and no clipping.
+ *   channel  the scalar s of a texel (r, g, b, a): RC2DGI_CH_R / _G / _B / _A that channel as it is, RC2DGI_CH_LUMA
+ *            ((0.2126f * r) + (0.7152f * g)) + (0.0722f * b): five single, unfused fp32 operations in that order.
+ *   edges    m ascending edges, 1 <= m <= RC2DGI_HIST_MAX_EDGES, as rc2dgi_check_edges admits them.
+ *   counts   record k is m + 4 32-bit words at counts + k * (m + 4): {status, texels, nan, bin[0] .. bin[m]}.
+ *            status is RC2DGI_STATS_OK and texels = w * h; a NaN scalar counts in nan, every other scalar, +-inf
+ *            included, in bin[bin(s)]: nan + the sum of the bins == texels.  An invalid rectangle yields status =
+ *            RC2DGI_STATS_INVALID (the word 0xFFFFFFFF) with every other word 0 and reads no texture memory; the other
+ *            records are unaffected.
+ * Determinism: the counts are integers, and integer addition gives the same words in any order.  That is the whole
+ * argument -- the kernel adds with integer atomics in whatever order the hardware schedules, and no float is ever
+ * accumulated.
+ * Calls.  `rects` and `edges` are host memory in both variants, read only during the call.  The call initialises every
+ * word of the n records itself: the caller's buffer may hold anything.  rc2dgi_histogram synchronises the context
+ * stream (a cascade chain timeout returns RC2DGI_E_DEVICE, as rc2dgi_compose does), runs the kernels over context-owned
+ * device buffers and copies the records back.  rc2dgi_histogram_device enqueues behind whatever frame is in flight
+ * and returns; counts_dev is a device pointer on the context's device, aligned to 4 bytes, that the caller keeps alive
+ * until rc2dgi_sync().  Up to 4 rectangles travel in the kernel's arguments, a longer list in batches as for
+ * rc2dgi_reduce_device (with the same remark on when such a call returns).  n == 0 is a successful no-op.
+ * Histogramming before the first frame is allowed (COLOR is then the input).
+ * Errors, each leaving the context valid: RC2DGI_E_ARG for a null context, a null pointer with n > 0, m outside
+ * 1 .. RC2DGI_HIST_MAX_EDGES, edges that rc2dgi_check_edges refuses, a bad channel or `which`, n < 0 or n > 1 << 20,
+ * (long long)n * (m + 4) > 1 << 26, a counts_dev not aligned to 4 bytes; RC2DGI_E_UNSUPPORTED on a row-strip shard.
+ * These calls only add exports: RC2DGI_ABI_VERSION stays 5. */
+enum { RC2DGI_CH_R = 0, RC2DGI_CH_G = 1, RC2DGI_CH_B = 2, RC2DGI_CH_A = 3, RC2DGI_CH_LUMA = 4 };
+int rc2dgi_histogram(rc2dgi_ctx *ctx, int which, int channel, const rc2dgi_rect *rects, int n, const float *edges, int m,
+                     unsigned *counts);
+int rc2dgi_histogram_device(rc2dgi_ctx *ctx, int which, int channel, const rc2dgi_rect *rects, int n, const float *edges,
+                            int m, void *counts_dev);
+
 /* cascade resolution (RC2DGI.cs:70-77), JFA step count (RC2DGI.cs:289-292) and which
  * giRT holds the final GI (1 or 2, RC2DGI.cs:365) */
 int rc2dgi_query(rc2dgi_ctx *ctx, int *cascade_w, int *cascade_h, int *jfa_steps, int *final_gi);
@@ -410,8 +499,8 @@ int rc2dgi_set_sky_table(rc2dgi_ctx *ctx, const float *rgb, int n);
  *                     starting when the upper tiles under its footprint are written (2: unrolled march);
  *                     4: the top level in that launch too; f32 cascades, one process.  A wait that times out
  *                     makes the next rc2dgi_sync / rc2dgi_download / rc2dgi_download_level / rc2dgi_compose /
- *                     rc2dgi_reduce / rc2dgi_do / rc2dgi_do_phase return RC2DGI_E_DEVICE and turns the chain off for
- *                     the context
+ *                     rc2dgi_reduce / rc2dgi_compose_tone / rc2dgi_histogram / rc2dgi_do / rc2dgi_do_phase return
+ *                     RC2DGI_E_DEVICE and turns the chain off for the context
  *                     (never a silent wrong frame)
  *   "rc_chain_spin"   diagnostic: polls per chain wait (0: the default bound; -1: every wait times out at once)
  *   "jfa_rows"        0 (default), 4, 8: the short isotropic JumpFlood steps (offsets 1, 2, 4 on square power-of-two

@@ -80,6 +80,8 @@ int rc2dgi_destroy(rc2dgi_ctx *c) {
   for (auto &ev : c->ev_jfa)
     if (ev) (void)hipEventDestroy(ev);
   free_buffers(c);
+  if (c->curves_dev) (void)hipFree(c->curves_dev);  // (the tone curves outlive a reallocation of the textures)
+  c->curves_dev = nullptr;
   for (auto &ev : c->ev)
     if (ev) (void)hipEventDestroy(ev);
   for (auto &ev : c->ev_level)

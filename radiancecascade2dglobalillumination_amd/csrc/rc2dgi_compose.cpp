@@ -1,7 +1,9 @@
 // rc2dgi_compose.cpp -- the display frame of the C ABI (include/rc2dgi.h): the reference's display layout
 // (RC2DGI.cs:139-163), and the views resolved to their stored textures for k_present (rc2dgi_present.hip).  The
 // queries too (rc2dgi_sample / rc2dgi_raycast, rc2dgi_query.hip): a point sample resolves its texture as a view does,
-// and so do the region statistics (rc2dgi_reduce, rc2dgi_reduce.hip), whose rectangles are planned here.
+// and so do the region statistics (rc2dgi_reduce, rc2dgi_reduce.hip), whose rectangles are planned here.  Last the
+// edge tables: the tone curves of the views (rc2dgi_set_curve / rc2dgi_compose_tone, rc2dgi_tone.hip) and the
+// histograms of rectangles (rc2dgi_histogram, rc2dgi_hist.hip), planned as the reductions are.
 #include "rc2dgi_ctx.h"
 
 #include <cstddef>
@@ -229,8 +231,11 @@ int reduce_args(rc2dgi_ctx *c, int which, const rc2dgi_rect *rects, int n, const
 
 // Validate the call and resolve every view to source pointer, pitch, axes, storage kind and filter, as
 // rc2dgi_download reads that texture.  Views that miss the window are dropped.
+// With `tones` (n records, or null) the tone of every kept view goes to `tn`, and *toned tells whether any differs from
+// {1.0f, 0}: where none does the call is rc2dgi_compose's own kernel.
 int resolve_views(rc2dgi_ctx *c, const rc2dgi_view *views, int n, int out_w, int out_h, const unsigned char *clear,
-                  const void *dst, int *pitch_bytes, PresentArgs &a) {
+                  const void *dst, int *pitch_bytes, PresentArgs &a, const rc2dgi_tone *tones = nullptr,
+                  ToneArgs *tn = nullptr, bool *toned = nullptr) {
   if (!c || !views || !dst) return fail(c, RC2DGI_E_ARG, "null argument");
   RC2DGI_USABLE(c);
   if (c->world > 1)
@@ -253,6 +258,13 @@ int resolve_views(rc2dgi_ctx *c, const rc2dgi_view *views, int n, int out_w, int
     if (q.w < 1 || q.h < 1) return fail(c, RC2DGI_E_ARG, tag + "w and h are at least 1");
     PresentView v{};
     if (int rc = resolve_texture(c, q.which, q.filter, tag, v)) return rc;
+    const rc2dgi_tone tone = tones ? tones[k] : rc2dgi_tone{1.0f, 0};
+    if (!(tone.exposure >= 0.0f) || std::isinf(tone.exposure))
+      return fail(c, RC2DGI_E_ARG, tag + "the exposure is finite and not negative");
+    if (tone.curve < 0 || tone.curve > RC2DGI_MAX_CURVES)
+      return fail(c, RC2DGI_E_ARG, tag + "the curve is 0 .. RC2DGI_MAX_CURVES");
+    if (tone.curve > 0 && c->curve_host[tone.curve - 1].empty())
+      return fail(c, RC2DGI_E_STATE, tag + "its curve slot is not set (rc2dgi_set_curve)");
     v.x = q.x;
     v.y = q.y;
     v.w = q.w;
@@ -272,8 +284,189 @@ int resolve_views(rc2dgi_ctx *c, const rc2dgi_view *views, int n, int out_w, int
       v.fy0 = clampi((long long)q.y + b, 0, out_h);
       v.fy1 = clampi(y1 - b, 0, out_h);
     }
+    if (tn) {
+      tn->exposure[a.n] = tone.exposure;
+      tn->curve[a.n] = tone.curve;
+      if (tone.curve > 0) tn->used |= 1u << (tone.curve - 1);
+      if (tone.exposure != 1.0f || tone.curve != 0) *toned = true;
+    }
     a.v[a.n++] = v;
   }
+  return RC2DGI_OK;
+}
+
+// ---- edge tables
+
+int check_edges(const float *e, int m) {
+  if (!e || m < 1) return RC2DGI_E_ARG;
+  for (int i = 0; i < m; ++i)
+    if (std::isnan(e[i]) || (i + 1 < m && e[i] > e[i + 1])) return RC2DGI_E_ARG;
+  return RC2DGI_OK;
+}
+
+// q8 as rc2dgi_device.h states it (the host's rintf rounds to nearest even, as v_rndne does)
+unsigned q8_host(float x) { return (unsigned)std::rint(std::fmin(std::fmax(x, 0.0f), 1.0f) * 255.0f); }
+
+float bits_float(uint32_t b) {
+  float f;
+  std::memcpy(&f, &b, 4);
+  return f;
+}
+
+// the two kernels of a display frame: k_present where no view is toned
+int launch_frame(rc2dgi_ctx *c, const PresentArgs &a, ToneArgs &tn, bool toned, void *dst, int pitch_bytes) {
+  if (!toned) {
+    HIPCHK(c, launch_present(a, dst, pitch_bytes, c->stream));
+    return RC2DGI_OK;
+  }
+  tn.tables = c->curves_dev;  // (a named slot is set, so the tables exist)
+  HIPCHK(c, launch_present_tone(a, tn, dst, pitch_bytes, c->stream));
+  return RC2DGI_OK;
+}
+
+int compose_device(rc2dgi_ctx *c, const rc2dgi_view *views, const rc2dgi_tone *tones, int n, int out_w, int out_h,
+                   const unsigned char *clear_rgba, void *dev, int pitch_bytes) {
+  PresentArgs a;
+  ToneArgs tn{};
+  bool toned = false;
+  if (int rc = resolve_views(c, views, n, out_w, out_h, clear_rgba, dev, &pitch_bytes, a, tones, &tn, &toned)) return rc;
+  if (reinterpret_cast<uintptr_t>(dev) % 4 != 0) return fail(c, RC2DGI_E_ARG, "the destination is aligned to 4 bytes");
+  HIPCHK(c, hipSetDevice(c->device));
+  return launch_frame(c, a, tn, toned, dev, pitch_bytes);
+}
+
+int compose_host(rc2dgi_ctx *c, const rc2dgi_view *views, const rc2dgi_tone *tones, int n, int out_w, int out_h,
+                 const unsigned char *clear_rgba, void *host, int pitch_bytes) {
+  PresentArgs a;
+  ToneArgs tn{};
+  bool toned = false;
+  if (int rc = resolve_views(c, views, n, out_w, out_h, clear_rgba, host, &pitch_bytes, a, tones, &tn, &toned)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = check_chain(c)) return rc;
+  const size_t dpitch = (size_t)round_up(out_w, 4) * 4, need = dpitch * (size_t)out_h;  // 16-byte rows: vector stores
+  if (need > c->present_cap) {  // (the stream is idle: nothing reads the old image)
+    if (c->present_buf) HIPCHK(c, hipFree(c->present_buf));
+    c->present_buf = nullptr;
+    c->present_cap = 0;
+    HIPCHK(c, alloc(&c->present_buf, need));
+    c->present_cap = need;
+  }
+  if (int rc = launch_frame(c, a, tn, toned, c->present_buf, (int)dpitch)) return rc;
+  HIPCHK(c, hipMemcpy2DAsync(host, (size_t)pitch_bytes, c->present_buf, dpitch, (size_t)out_w * 4, (size_t)out_h,
+                             hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RC2DGI_OK;
+}
+
+// ---- histograms (rc2dgi_hist.hip): the host validates the rectangles and cuts them into row blocks
+
+// the device side: the tree of the edges, then one batch of work items -- a fixed size whatever the call
+constexpr size_t kHistTreeBytes = (size_t)kHistTreeWords * sizeof(float);
+constexpr size_t hist_bytes = kHistTreeBytes + (size_t)kHistBatch * sizeof(HistItem);
+
+// Rows of a block of a w x h rectangle: a 1024th of the rectangle, but between kHistMinItemTexels and kHistItemTexels
+// texels (a texture of any size then spreads over the device, and a large one does not flush a record's counters more
+// often than it must), in whole passes of the workgroup (256 / lanes-a-row rows when the rows are narrow, k_hist), at
+// most kHistMaxBlocks blocks a rectangle.  Any cut gives the same counts.
+int hist_block_rows(int w, int h) {
+  long long gr = 1;
+  if (w <= 1024) {
+    int lr = 1;
+    while (lr * 4 < w) lr <<= 1;
+    gr = 256 / lr;
+  }
+  const long long target =
+      std::min<long long>(std::max<long long>((long long)w * h / 1024, kHistMinItemTexels), kHistItemTexels);
+  long long rows = (target + w - 1) / w;
+  rows = (rows + gr - 1) / gr * gr;
+  while ((h + rows - 1) / rows > kHistMaxBlocks) rows <<= 1;
+  return (int)std::min<long long>(rows, 1 << 30);
+}
+
+// n >= 1 rectangles of t into the device records counts_dev, enqueued on the context stream: the launches that store
+// the tree (the first one clears the records too), then one launch an inline plan or a batch.
+int hist_enqueue(rc2dgi_ctx *c, const TexSource &t, int channel, const rc2dgi_rect *rects, int n, const float *edges,
+                 int m, void *counts_dev) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->hist_buf) HIPCHK(c, alloc(&c->hist_buf, hist_bytes));
+  float *tree_dev = reinterpret_cast<float *>(c->hist_buf);
+  HistItem *items_dev = reinterpret_cast<HistItem *>(c->hist_buf + kHistTreeBytes);
+  const int levels = tree_levels(m), words = 1 << levels;
+  float tree[kHistTreeWords];
+  tree_layout(edges, m, levels, std::numeric_limits<float>::quiet_NaN(), tree);
+  for (int w0 = 0; w0 < words; w0 += kTableChunk) {
+    TableChunk ch;
+    const int nw = std::min(kTableChunk, words - w0);
+    std::memcpy(ch.v, tree + w0, (size_t)nw * sizeof(float));
+    HIPCHK(c, launch_store_table(ch, nw, tree_dev + w0, w0 == 0 ? static_cast<unsigned *>(counts_dev) : nullptr,
+                                 w0 == 0 ? (size_t)n * (size_t)(m + 4) : 0, c->stream));
+  }
+  const HistTable tab{tree_dev, levels, m, channel};
+  if (n <= kHistInline) {  // the plan fits the kernel's arguments: no upload
+    HistInline inl{};
+    inl.n = n;
+    int items = 0;
+    for (int k = 0; k < n; ++k) {
+      const rc2dgi_rect &r = rects[k];
+      int nb = 1;
+      inl.d[k] = HistDesc{0, 0, 0, 0, 1, items, k, 0};
+      if (rect_valid(r, t.nx, t.ny)) {
+        const int rows = hist_block_rows(r.w, r.h);
+        nb = (int)(((long long)r.h + rows - 1) / rows);
+        inl.d[k] = HistDesc{r.x, r.y, r.w, r.h, rows, items, k, 0};
+      }
+      items += nb;
+    }
+    HIPCHK(c, launch_hist(t, inl, nullptr, items, tab, counts_dev, c->stream));
+    return RC2DGI_OK;
+  }
+  // One batch of host items at a time, as reduce_enqueue: the copy of a flush has consumed the vector when it returns.
+  const HistInline none{};
+  std::vector<HistItem> b;
+  auto flush = [&]() -> int {
+    if (b.empty()) return RC2DGI_OK;
+    HIPCHK(c, hipMemcpyAsync(items_dev, b.data(), b.size() * sizeof(HistItem), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_hist(t, none, items_dev, (int)b.size(), tab, counts_dev, c->stream));
+    b.clear();
+    return RC2DGI_OK;
+  };
+  for (int k = 0; k < n; ++k) {
+    const rc2dgi_rect &r = rects[k];
+    if (!rect_valid(r, t.nx, t.ny)) {
+      if (b.size() + 1 > (size_t)kHistBatch)
+        if (int rc = flush()) return rc;
+      b.push_back(HistItem{0, 0, 0, 0, 0, 0, (unsigned)k | kHistSingle | kHistFirst});
+      continue;
+    }
+    const int rows = hist_block_rows(r.w, r.h);
+    const int nb = (int)(((long long)r.h + rows - 1) / rows);
+    for (int i = 0; i < nb; ++i) {  // (the blocks of a rectangle may fall into different batches: they only add)
+      if (b.size() + 1 > (size_t)kHistBatch)
+        if (int rc = flush()) return rc;
+      b.push_back(HistItem{r.x, r.y, r.w, i * rows, (int)std::min<long long>((long long)(i + 1) * rows, r.h), r.w * r.h,
+                           (unsigned)k | (nb == 1 ? kHistSingle : 0u) | (i == 0 ? kHistFirst : 0u)});
+    }
+  }
+  return flush();
+}
+
+// the checks the two calls share; n == 0 is left to the caller (a successful no-op)
+int hist_args(rc2dgi_ctx *c, int which, int channel, const rc2dgi_rect *rects, int n, const float *edges, int m,
+              const void *counts, TexSource &t) {
+  if (!c) return RC2DGI_E_ARG;
+  RC2DGI_USABLE(c);
+  if (n < 0 || n > kHistMax) return fail(c, RC2DGI_E_ARG, "histogram: n is 0 .. 1 << 20");
+  if (m < 1 || m > RC2DGI_HIST_MAX_EDGES) return fail(c, RC2DGI_E_ARG, "histogram: m is 1 .. RC2DGI_HIST_MAX_EDGES");
+  if ((long long)n * (m + 4) > kHistMaxWords) return fail(c, RC2DGI_E_ARG, "histogram: n * (m + 4) is at most 1 << 26");
+  if (check_edges(edges, m) != RC2DGI_OK)
+    return fail(c, RC2DGI_E_ARG, "histogram: the edges are m ascending floats, none a NaN (rc2dgi_check_edges)");
+  if (channel < RC2DGI_CH_R || channel > RC2DGI_CH_LUMA) return fail(c, RC2DGI_E_ARG, "histogram: bad channel");
+  if (n > 0 && (!rects || !counts)) return fail(c, RC2DGI_E_ARG, "histogram: null argument");
+  if (int rc = resolve_texture(c, which, RC2DGI_FILTER_POINT, "histogram: ", t)) return rc;
+  if (c->world > 1)
+    return fail(c, RC2DGI_E_UNSUPPORTED,
+                "a row-strip shard's textures hold windows and bands: histogram on an unsharded context");
   return RC2DGI_OK;
 }
 
@@ -302,32 +495,84 @@ int rc2dgi_display_layout(const rc2dgi_config *cfg, rc2dgi_view *views, int max_
 
 int rc2dgi_compose_device(rc2dgi_ctx *c, const rc2dgi_view *views, int n, int out_w, int out_h,
                           const unsigned char *clear_rgba, void *dev, int pitch_bytes) {
-  PresentArgs a;
-  if (int rc = resolve_views(c, views, n, out_w, out_h, clear_rgba, dev, &pitch_bytes, a)) return rc;
-  if (reinterpret_cast<uintptr_t>(dev) % 4 != 0) return fail(c, RC2DGI_E_ARG, "the destination is aligned to 4 bytes");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, launch_present(a, dev, pitch_bytes, c->stream));
-  return RC2DGI_OK;
+  return compose_device(c, views, nullptr, n, out_w, out_h, clear_rgba, dev, pitch_bytes);
 }
 
 int rc2dgi_compose(rc2dgi_ctx *c, const rc2dgi_view *views, int n, int out_w, int out_h, const unsigned char *clear_rgba,
                    void *host, int pitch_bytes) {
-  PresentArgs a;
-  if (int rc = resolve_views(c, views, n, out_w, out_h, clear_rgba, host, &pitch_bytes, a)) return rc;
+  return compose_host(c, views, nullptr, n, out_w, out_h, clear_rgba, host, pitch_bytes);
+}
+
+// ---- edge tables, toned views (rc2dgi_tone.hip)
+int rc2dgi_check_edges(const float *edges, int m) { return check_edges(edges, m); }
+
+int rc2dgi_curve_q8(float *edges255) {
+  if (!edges255) return RC2DGI_E_ARG;
+  for (unsigned k = 1; k <= 255u; ++k) {
+    // the smallest bit pattern in [0, bits(1.0f)] whose float has q8 >= k: q8 is monotone there, q8(1.0f) = 255
+    uint32_t lo = 0u, hi = 0x3F800000u;
+    while (lo < hi) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (q8_host(bits_float(mid)) >= k) hi = mid;
+      else lo = mid + 1;
+    }
+    edges255[k - 1] = bits_float(lo);
+  }
+  return RC2DGI_OK;
+}
+
+int rc2dgi_set_curve(rc2dgi_ctx *c, int slot, const float *edges255) {
+  if (!c) return RC2DGI_E_ARG;
+  RC2DGI_USABLE(c);
+  if (slot < 1 || slot > RC2DGI_MAX_CURVES) return fail(c, RC2DGI_E_ARG, "set_curve: the slot is 1 .. RC2DGI_MAX_CURVES");
+  if (!edges255) {
+    c->curve_host[slot - 1].clear();  // (the device table stays: a compose enqueued earlier still reads it)
+    return RC2DGI_OK;
+  }
+  if (check_edges(edges255, RC2DGI_CURVE_EDGES) != RC2DGI_OK)
+    return fail(c, RC2DGI_E_ARG, "set_curve: 255 ascending edges, none a NaN (rc2dgi_check_edges)");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->curves_dev) HIPCHK(c, alloc(&c->curves_dev, (size_t)RC2DGI_MAX_CURVES * kCurveWords * sizeof(float)));
+  std::vector<float> copy(edges255, edges255 + RC2DGI_CURVE_EDGES);
+  TableChunk ch;
+  tree_layout(copy.data(), RC2DGI_CURVE_EDGES, kCurveLevels, std::numeric_limits<float>::infinity(), ch.v);
+  HIPCHK(c, launch_store_table(ch, kCurveWords, c->curves_dev + (size_t)(slot - 1) * kCurveWords, nullptr, 0, c->stream));
+  c->curve_host[slot - 1].swap(copy);
+  return RC2DGI_OK;
+}
+
+int rc2dgi_compose_tone_device(rc2dgi_ctx *c, const rc2dgi_view *views, const rc2dgi_tone *tones, int n, int out_w,
+                               int out_h, const unsigned char *clear_rgba, void *dev, int pitch_bytes) {
+  return compose_device(c, views, tones, n, out_w, out_h, clear_rgba, dev, pitch_bytes);
+}
+
+int rc2dgi_compose_tone(rc2dgi_ctx *c, const rc2dgi_view *views, const rc2dgi_tone *tones, int n, int out_w, int out_h,
+                        const unsigned char *clear_rgba, void *host, int pitch_bytes) {
+  return compose_host(c, views, tones, n, out_w, out_h, clear_rgba, host, pitch_bytes);
+}
+
+// ---- histograms (rc2dgi_hist.hip)
+int rc2dgi_histogram_device(rc2dgi_ctx *c, int which, int channel, const rc2dgi_rect *rects, int n, const float *edges,
+                            int m, void *counts_dev) {
+  TexSource t{};
+  if (int rc = hist_args(c, which, channel, rects, n, edges, m, counts_dev, t)) return rc;
+  if (n == 0) return RC2DGI_OK;
+  if (!aligned_to(counts_dev, 4)) return fail(c, RC2DGI_E_ARG, "histogram: the records are aligned to 4 bytes");
+  return hist_enqueue(c, t, channel, rects, n, edges, m, counts_dev);
+}
+
+int rc2dgi_histogram(rc2dgi_ctx *c, int which, int channel, const rc2dgi_rect *rects, int n, const float *edges, int m,
+                     unsigned *counts) {
+  TexSource t{};
+  if (int rc = hist_args(c, which, channel, rects, n, edges, m, counts, t)) return rc;
+  if (n == 0) return RC2DGI_OK;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (int rc = check_chain(c)) return rc;
-  const size_t dpitch = (size_t)round_up(out_w, 4) * 4, need = dpitch * (size_t)out_h;  // 16-byte rows: vector stores
-  if (need > c->present_cap) {  // (the stream is idle: nothing reads the old image)
-    if (c->present_buf) HIPCHK(c, hipFree(c->present_buf));
-    c->present_buf = nullptr;
-    c->present_cap = 0;
-    HIPCHK(c, alloc(&c->present_buf, need));
-    c->present_cap = need;
-  }
-  HIPCHK(c, launch_present(a, c->present_buf, (int)dpitch, c->stream));
-  HIPCHK(c, hipMemcpy2DAsync(host, (size_t)pitch_bytes, c->present_buf, dpitch, (size_t)out_w * 4, (size_t)out_h,
-                             hipMemcpyDeviceToHost, c->stream));
+  const size_t bytes = (size_t)n * (size_t)(m + 4) * sizeof(unsigned);
+  if (int rc = query_buffer(c, c->query_out, c->query_out_cap, bytes)) return rc;
+  if (int rc = hist_enqueue(c, t, channel, rects, n, edges, m, c->query_out)) return rc;
+  HIPCHK(c, hipMemcpyAsync(counts, c->query_out, bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RC2DGI_OK;
 }

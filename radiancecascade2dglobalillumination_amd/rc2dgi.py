@@ -143,6 +143,39 @@ def _rect_array(rects):
     return a.reshape(-1).view(RECT_DTYPE)
 
 
+class Tone(ctypes.Structure):
+    """rc2dgi_tone: how a view's colour channels become bytes -- T(c * exposure), T = q8 for curve 0, else bin() over
+    the 255 edges of that curve slot (RC2DGI.set_curve).  Alpha and the border are not toned."""
+    _fields_ = [("exposure", ctypes.c_float), ("curve", ctypes.c_int)]
+
+
+CURVE_EDGES, MAX_CURVES, HIST_MAX_EDGES = 255, 8, 1023
+CHANNELS = {"r": 0, "g": 1, "b": 2, "a": 3, "luma": 4}
+HIST_HEAD = 3  # words of a histogram record before bin[0]: status, texels, nan
+
+
+def _tone_array(tones, n):
+    """tones as a ctypes array of n Tone: Tone records, (exposure, curve) pairs or bare exposures; None stays None."""
+    if tones is None:
+        return None
+    if len(tones) != n:
+        raise ValueError(f"compose: {n} views and {len(tones)} tones")
+    arr = (Tone * max(n, 1))()
+    for k, t in enumerate(tones):
+        if isinstance(t, Tone):
+            arr[k] = t
+        elif isinstance(t, (tuple, list)):
+            arr[k] = Tone(float(t[0]), int(t[1]))
+        else:
+            arr[k] = Tone(float(t), 0)
+    return arr
+
+
+def _edge_array(edges):
+    e = np.ascontiguousarray(edges, np.float32).reshape(-1)
+    return e, e.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
 def _view_array(views):
     arr = (View * max(len(views), 1))()
     for k, v in enumerate(views):
@@ -228,6 +261,16 @@ def load_library(path: Optional[str] = None):
         "rc2dgi_raycast_device": ([vp, vp, ctypes.c_int, vp], ctypes.c_int),
         "rc2dgi_reduce": ([vp, ctypes.c_int, vp, ctypes.c_int, vp], ctypes.c_int),
         "rc2dgi_reduce_device": ([vp, ctypes.c_int, vp, ctypes.c_int, vp], ctypes.c_int),
+        "rc2dgi_check_edges": ([fp, ctypes.c_int], ctypes.c_int),
+        "rc2dgi_curve_q8": ([fp], ctypes.c_int),
+        "rc2dgi_set_curve": ([vp, ctypes.c_int, fp], ctypes.c_int),
+        "rc2dgi_compose_tone": ([vp, ctypes.POINTER(View), ctypes.POINTER(Tone), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                 ctypes.POINTER(ctypes.c_ubyte), vp, ctypes.c_int], ctypes.c_int),
+        "rc2dgi_compose_tone_device": ([vp, ctypes.POINTER(View), ctypes.POINTER(Tone), ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), vp, ctypes.c_int], ctypes.c_int),
+        "rc2dgi_histogram": ([vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, fp, ctypes.c_int, vp], ctypes.c_int),
+        "rc2dgi_histogram_device": ([vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, fp, ctypes.c_int, vp],
+                                    ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -420,17 +463,34 @@ class RC2DGI:
         cl = None if clear is None else (ctypes.c_ubyte * 4)(*[int(v) for v in clear])
         return _view_array(views), len(views), w, h, cl
 
-    def compose(self, views, size=None, clear=None) -> np.ndarray:
+    def set_curve(self, slot: int, edges) -> None:
+        """The tone curve of slot 1 .. MAX_CURVES (rc2dgi_set_curve): 255 ascending float32 edges, a view toned with it
+        shows byte bin(c * exposure) = the number of edges <= the value (curve_q8 / curve_from make such tables).
+        Ordered on the context stream: a compose enqueued before keeps the old curve.  None clears the slot."""
+        if edges is None:
+            self._check(self._L.rc2dgi_set_curve(self._h, int(slot), None), "set_curve")
+            return
+        e, p = _edge_array(edges)
+        if e.size != CURVE_EDGES:
+            raise ValueError(f"set_curve: expected {CURVE_EDGES} edges, got {e.size}")
+        self._check(self._L.rc2dgi_set_curve(self._h, int(slot), p), "set_curve")
+
+    def compose(self, views, size=None, clear=None, tones=None) -> np.ndarray:
         """The window (RC2DGI.cs:135-165) as one RGBA8 image uint8[h, w, 4], row 0 = top: `clear` (default
         opaque black), then the views in order (View, or tuples for View.make), blended in 8 bits
-        (rc2dgi_compose).  size: (w, h), default the screen.  Synchronous."""
+        (rc2dgi_compose).  size: (w, h), default the screen.  Synchronous.
+        tones: one Tone, (exposure, curve) pair or exposure a view (rc2dgi_compose_tone); None: untoned."""
         arr, n, w, h, cl = self._compose_args(views, size, clear)
         out = np.empty((max(h, 0), max(w, 0), 4), np.uint8)
-        self._check(self._L.rc2dgi_compose(self._h, arr, n, w, h, cl, out.ctypes.data_as(ctypes.c_void_p), w * 4),
-                    "compose")
+        dst = out.ctypes.data_as(ctypes.c_void_p)
+        if tones is None:
+            self._check(self._L.rc2dgi_compose(self._h, arr, n, w, h, cl, dst, w * 4), "compose")
+        else:
+            self._check(self._L.rc2dgi_compose_tone(self._h, arr, _tone_array(tones, n), n, w, h, cl, dst, w * 4),
+                        "compose")
         return out
 
-    def compose_into(self, dst, views, size=None, clear=None, pitch=None) -> None:
+    def compose_into(self, dst, views, size=None, clear=None, pitch=None, tones=None) -> None:
         """The same image into device memory, enqueued on the context stream (rc2dgi_compose_device; sync()
         or order the stream before reading).  dst: a torch uint8 tensor [h, w, 4] on this context's GPU --
         its rows may be padded, the pitch is the tensor's row stride -- or a device pointer (int) with
@@ -449,8 +509,13 @@ class RC2DGI:
         else:
             ptr = int(dst)
         arr, n, w, h, cl = self._compose_args(views, size, clear)
-        self._check(self._L.rc2dgi_compose_device(self._h, arr, n, w, h, cl, ctypes.c_void_p(ptr),
-                                                  int(pitch) if pitch else 0), "compose_into")
+        if tones is None:
+            self._check(self._L.rc2dgi_compose_device(self._h, arr, n, w, h, cl, ctypes.c_void_p(ptr),
+                                                      int(pitch) if pitch else 0), "compose_into")
+        else:  # (as compose: one tone a view)
+            self._check(self._L.rc2dgi_compose_tone_device(self._h, arr, _tone_array(tones, n), n, w, h, cl,
+                                                           ctypes.c_void_p(ptr), int(pitch) if pitch else 0),
+                        "compose_into")
 
     def display_frame(self, thumbnails: bool = True) -> np.ndarray:
         """The reference's display: colorRT over the window and, with `thumbnails`, its seven debug views."""
@@ -556,6 +621,41 @@ class RC2DGI:
         w = RT[which] if isinstance(which, str) else int(which)
         self._check(self._L.rc2dgi_reduce_device(self._h, w, a.ctypes.data_as(ctypes.c_void_p), a.shape[0],
                                                  ctypes.c_void_p(dst.data_ptr())), "reduce_into")
+
+    # ---------------------------------------------------------------- histograms of rectangles
+    def _hist_args(self, which, edges, channel, rects):
+        w = RT[which] if isinstance(which, str) else int(which)
+        if rects is None:
+            tw, th = self.texture_size(w)
+            rects = [[0, 0, tw, th]]
+        ch = CHANNELS[channel] if isinstance(channel, str) else int(channel)
+        e, ep = _edge_array(edges)
+        return w, ch, _rect_array(rects), e, ep
+
+    def histogram(self, which, edges, channel="luma", rects=None):
+        """Per rectangle the counts of its texels by bin of the ascending `edges` (rc2dgi_histogram): bin(s) = the number
+        of edges <= s, s the texel's channel "r" / "g" / "b" / "a" or its "luma".  rects as for reduce; None: the whole
+        texture.  Returns an (n, m + 4) uint32 array, a row {status, texels, nan, bin[0] .. bin[m]}, synchronously; an
+        invalid rectangle has status 0xFFFFFFFF (STATS_INVALID) and zeros."""
+        w, ch, a, e, ep = self._hist_args(which, edges, channel, rects)
+        out = np.zeros((a.shape[0], e.size + 4), np.uint32)
+        self._check(self._L.rc2dgi_histogram(self._h, w, ch, a.ctypes.data_as(ctypes.c_void_p), a.shape[0], ep, e.size,
+                                             out.ctypes.data_as(ctypes.c_void_p)), "histogram")
+        return out
+
+    def histogram_into(self, dst, which, edges, channel="luma", rects=None) -> None:
+        """The same records into device memory, enqueued on the context stream after whatever frame is in flight
+        (rc2dgi_histogram_device; sync() or order the stream before reading).  dst: a contiguous int32 (n, m + 4) torch
+        tensor on this context's GPU; every word of it is written.  rects and edges: host memory, as for histogram."""
+        if not getattr(dst, "is_cuda", False) or dst.device.index != self.device:
+            raise TypeError("histogram_into: expected a tensor on this context's GPU")
+        if str(dst.dtype) != "torch.int32" or not dst.is_contiguous():
+            raise TypeError("histogram_into: expected a contiguous int32 tensor")
+        w, ch, a, e, ep = self._hist_args(which, edges, channel, rects)
+        if dst.dim() != 2 or dst.shape[1] != e.size + 4 or dst.shape[0] != a.shape[0]:
+            raise ValueError(f"histogram_into: expected shape ({a.shape[0]}, {e.size + 4}), got {tuple(dst.shape)}")
+        self._check(self._L.rc2dgi_histogram_device(self._h, w, ch, a.ctypes.data_as(ctypes.c_void_p), a.shape[0], ep,
+                                                    e.size, ctypes.c_void_p(dst.data_ptr())), "histogram_into")
 
     def set_tuning(self, key: str, value: int) -> None:
         """Performance knobs (results are identical for every value), e.g. rc_variant."""
@@ -711,6 +811,61 @@ def display_layout(W: int, H: int, max_views: int = 8):
     return [View.from_buffer_copy(arr[k]) for k in range(min(n, max_views))]
 
 
+def check_edges(edges) -> bool:
+    """Host-only: whether `edges` is a valid edge table (rc2dgi_check_edges): at least one float32, ascending (repeats,
+    +-inf and -0.0 allowed), no NaN."""
+    e, p = _edge_array(edges)
+    return load_library().rc2dgi_check_edges(p if e.size else None, int(e.size)) == 0
+
+
+def curve_q8() -> np.ndarray:
+    """Host-only: the 255 edges whose bin() is q8(x) = rint(clamp(x, 0, 1) * 255) for every float (rc2dgi_curve_q8)."""
+    e = np.empty(CURVE_EDGES, np.float32)
+    rc = load_library().rc2dgi_curve_q8(_fp(e))
+    if rc != 0:
+        raise RC2DGIError(rc, "rc2dgi_curve_q8")
+    return e
+
+
+def curve_from(fn) -> np.ndarray:
+    """Host-only: the 255 edges of the tone curve byte(x) = q8(fn(x)) for a monotone (non-decreasing) fn, evaluated in
+    float64 on arrays: edge k - 1 is the smallest non-negative float32 x with rint(255 * fn(x)) >= k, found by
+    bisection over float bit patterns (the bits of a non-negative float order as the float does); +inf where no finite
+    x reaches k.  fn's float64 result is rounded to float32 and the product with 255 is the float32 one, as q8 forms
+    it, so that the curve shows exactly the byte the untoned path would show for fn(x): curve_from(lambda x: x) is
+    curve_q8()."""
+    k = np.arange(1, CURVE_EDGES + 1, dtype=np.float64)
+    top = 0x7F800000  # +inf: the answer when no finite float reaches k
+    lo, hi = np.zeros(CURVE_EDGES, np.int64), np.full(CURVE_EDGES, top, np.int64)
+    while (lo < hi).any():
+        mid = (lo + hi) // 2
+        x = mid.astype(np.uint32).view(np.float32).astype(np.float64)
+        with np.errstate(all="ignore"):
+            y = np.asarray(fn(np.where(np.isfinite(x), x, np.finfo(np.float32).max)), np.float64)
+        y32 = np.clip(y, 0.0, 1.0).astype(np.float32)  # (a NaN of fn stays one and reaches no k)
+        ok = (np.rint(y32 * np.float32(255.0)) >= k) | (mid >= top)
+        hi = np.where(ok & (lo < hi), mid, hi)
+        lo = np.where(~ok & (lo < hi), mid + 1, lo)
+    return lo.astype(np.uint32).view(np.float32).copy()
+
+
+def percentile(hist_record, edges, p: float) -> float:
+    """The value below which the fraction p (0 .. 1) of a histogram's non-NaN texels lie, to the resolution of the
+    edges: the edge at which the running count of the bins first reaches p of texels - nan.  hist_record: one row of
+    RC2DGI.histogram.  Bin 0 lies below every edge (it returns edges[0]); the last bin has no upper edge (edges[-1]).
+    NaN for a record without a counted texel."""
+    rec = np.asarray(hist_record).reshape(-1).astype(np.int64)
+    e = np.asarray(edges, np.float32).reshape(-1)
+    if rec.size != e.size + 4:
+        raise ValueError(f"percentile: a record of {e.size} edges has {e.size + 4} words, got {rec.size}")
+    total = int(rec[1] - rec[2])
+    if rec[0] != STATS_OK or total <= 0:
+        return float("nan")
+    run = np.cumsum(rec[HIST_HEAD:])
+    b = int(np.searchsorted(run, max(p * total, 1e-300), side="left"))
+    return float(e[min(b, e.size - 1)])
+
+
 def plan_rows(W: int, H: int, N: int, blur_radius: float, rank: int, world: int, pass_id: int,
               render_scale: float = 1.0):
     """Host-only planner: [(begin, end), ...] rows shard `rank` of `world` computes for a pass
@@ -775,4 +930,5 @@ __all__ = ["RC2DGI", "RC2DGIError", "load_library", "abi_version", "RT", "PASS_N
            "View", "display_layout", "FILTER_RT", "FILTER_POINT", "FILTER_LINEAR", "MAX_VIEWS", "Ray", "RayHit",
            "RAY_DTYPE", "HIT_DTYPE", "hit_floats", "RAY_INVALID", "RAY_RANGE", "RAY_EDGE", "RAY_EMISSIVE", "RAY_SURFACE",
            "RAY_STEPS", "Rect", "Stats", "RECT_DTYPE", "STATS_DTYPE", "stats_view", "STATS_OK", "STATS_INVALID",
-           "STATS_WORDS", "REDUCE_MAX"]
+           "STATS_WORDS", "REDUCE_MAX", "Tone", "CURVE_EDGES", "MAX_CURVES", "HIST_MAX_EDGES", "CHANNELS", "HIST_HEAD",
+           "check_edges", "curve_q8", "curve_from", "percentile"]
