@@ -16,7 +16,7 @@ static unsafe class RC2DGINative
 
     public const int OK = 0;
     public enum RT { Color = 0, Emissive = 1, Jump1 = 2, Jump2 = 3, Dist = 4, GI1 = 5, GI2 = 6, Temp = 7, Blur = 8, FinalGI = 9 }
-    public enum Format { RGBA8 = 0, RGBA32F = 1 }
+    public enum Format { RGBA8 = 0, RGBA32F = 1, RGBA16F = 2 }  // RGBA16F: rc2dgi_read / rc2dgi_read_device only
     public enum Storage { F32 = 0, RGBA8Compat = 1, F16 = 2 }  // RGBA8Compat: the shipped app's RGBA8 textures, byte-exact
 
     [StructLayout(LayoutKind.Sequential)]
@@ -130,6 +130,13 @@ static unsafe class RC2DGINative
     [DllImport(Lib)] public static extern int rc2dgi_compose_tone_device(IntPtr ctx, View* views, Tone* tones, int n, int outW, int outH, byte* clearRgba, void* dev, int pitchBytes);
     [DllImport(Lib)] public static extern int rc2dgi_histogram(IntPtr ctx, int which, int channel, TexRect* rects, int n, float* edges, int m, uint* counts);
     [DllImport(Lib)] public static extern int rc2dgi_histogram_device(IntPtr ctx, int which, int channel, TexRect* rects, int n, float* edges, int m, void* countsDev);
+
+    // A rectangle of a render texture as an image converted on the device (rect null: the whole texture): RGBA32F,
+    // RGBA16F (round to nearest even) or RGBA8 (q8) pixels in rows of pitchBytes (0: tight).  With ReadFlip image row 0
+    // is the rectangle's top row, the order rc2dgi_compose writes.  dev: aligned to a pixel, as pitchBytes is.
+    public const int ReadFlip = 1;
+    [DllImport(Lib)] public static extern int rc2dgi_read(IntPtr ctx, int which, TexRect* rect, int format, int flags, void* host, int pitchBytes);
+    [DllImport(Lib)] public static extern int rc2dgi_read_device(IntPtr ctx, int which, TexRect* rect, int format, int flags, void* dev, int pitchBytes);
 
     static IntPtr ctx;
     static Config config;

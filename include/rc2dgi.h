@@ -62,7 +62,7 @@ typedef enum rc2dgi_status {
   RC2DGI_E_STATE = -6,        /* call not valid in the current state */
   RC2DGI_E_DEVICE = -7        /* a device-side check failed: an enqueued frame's results are wrong (the cascade
                                  chain's wait timed out; reported by the next rc2dgi_sync / _download /
-                                 _download_level / _compose / _reduce / _compose_tone / _histogram / _do /
+                                 _download_level / _compose / _reduce / _compose_tone / _histogram / _read / _do /
                                  _do_phase) */
 } rc2dgi_status;
 
@@ -97,7 +97,10 @@ typedef enum rc2dgi_flag {
 
 typedef enum rc2dgi_format {
   RC2DGI_FMT_RGBA8 = 0,    /* 4 x uint8, unorm (k/255) */
-  RC2DGI_FMT_RGBA32F = 1   /* 4 x float32 */
+  RC2DGI_FMT_RGBA32F = 1,  /* 4 x float32 */
+  RC2DGI_FMT_RGBA16F = 2   /* 4 x IEEE binary16; accepted by rc2dgi_read / rc2dgi_read_device only: rc2dgi_upload,
+                              rc2dgi_upload_device, rc2dgi_download and rc2dgi_download_level know the two formats
+                              above and refuse this one with RC2DGI_E_ARG */
 } rc2dgi_format;
 
 typedef struct rc2dgi_config {
@@ -431,6 +434,45 @@ int rc2dgi_histogram(rc2dgi_ctx *ctx, int which, int channel, const rc2dgi_rect 
 int rc2dgi_histogram_device(rc2dgi_ctx *ctx, int which, int channel, const rc2dgi_rect *rects, int n, const float *edges,
                             int m, void *counts_dev);
 
+/* ---- a rectangle of a render texture as an image, converted on the device.  (The HDR final GI as a tensor for a
+ * PyTorch consumer, a sprite-sized crop of it for the host, a frame saved as half floats -- without rc2dgi_download's
+ * copy of the whole texture at 16 bytes a texel and its conversion on one host thread.)
+ *   which, rect   as for rc2dgi_reduce: any rc2dgi_rt, RC2DGI_RT_FINAL_GI included; texels in GL order (row 0 = the
+ *            bottom); valid when w >= 1, h >= 1, x >= 0, y >= 0, w <= TW - x and h <= TH - y (compared in this form).
+ *            rect == NULL is the whole texture.  There is no wrap and no clipping.  One call is one image: an invalid
+ *            rectangle is RC2DGI_E_ARG and nothing is written (it is not a per-record status).
+ *   Pixels   pixel (i, j) of the image, 0 <= i < w, 0 <= j < h, is texel (x + i, y + j); with RC2DGI_READ_FLIP in
+ *            `flags` it is texel (x + i, y + h - 1 - j): image row 0 is the rectangle's TOP row, the window's order, as
+ *            rc2dgi_compose writes.  The texel's value is what rc2dgi_download returns for it as floats, through the
+ *            decoder the views use -- the list under rc2dgi_compose (JUMP1 / JUMP2 decoded, DIST its hi / lo bytes,
+ *            COLOR the input before the first frame and the merged output after, GI2 (0, 0, 0, 1) with one cascade,
+ *            FINAL_GI the alias).
+ *   Formats  RC2DGI_FMT_RGBA32F: the four floats as they are (a NaN stays a NaN; its payload is not part of the
+ *            contract).  RC2DGI_FMT_RGBA8: q8 per channel, rint(clamp(x, 0, 1) * 255), NaN -> 0: the bytes
+ *            rc2dgi_download(.., RC2DGI_FMT_RGBA8) gives.  RC2DGI_FMT_RGBA16F: each float converted to IEEE binary16
+ *            with round to nearest, ties to even -- magnitudes from 65520 up become +-inf, results below 2^-14 are
+ *            binary16 subnormals (not flushed), magnitudes up to 2^-25 become +-0 (the sign of zero is kept), a NaN
+ *            becomes a NaN (payload unspecified): what numpy's and torch's float32 -> float16 do.  It is not the
+ *            round-toward-zero pack that RC2DGI_STORAGE_F16 stores with.
+ *   Pitch    pitch_bytes == 0 is a tight row: w * 16, w * 8 or w * 4 bytes.  Bytes of a row past that, and rows past
+ *            h, are not written.  rc2dgi_read_device requires `dev` aligned to a pixel (16 / 8 / 4 bytes for RGBA32F /
+ *            RGBA16F / RGBA8) and pitch_bytes a multiple of that; the host variant has no alignment rule.
+ * Calls.  rc2dgi_read synchronises the context stream (a cascade chain timeout returns RC2DGI_E_DEVICE, as
+ * rc2dgi_compose does), runs the kernel into a context-owned staging buffer and copies the rows out.  The staging is
+ * 8 MiB of device memory whatever the image, allocated at the first call and freed with the context: a larger
+ * rectangle goes through it in blocks of whole rows.  rc2dgi_read_device enqueues the kernel on the context stream,
+ * after whatever frame is in flight, and returns; `dev` is a device pointer on the context's device that the caller
+ * keeps alive until rc2dgi_sync().  Reading before the first frame is allowed (COLOR is then the input).
+ * Errors, each leaving the context valid and the destination untouched: RC2DGI_E_ARG for a null context or
+ * destination, a bad `which` or `format`, a flag bit other than RC2DGI_READ_FLIP, an invalid rectangle, a pitch smaller
+ * than a row and, for the device variant, a misaligned pointer or pitch; RC2DGI_E_UNSUPPORTED on a row-strip shard
+ * (world > 1: its textures hold windows and bands).  These calls only add exports: RC2DGI_ABI_VERSION stays 5. */
+enum { RC2DGI_READ_FLIP = 1 };
+int rc2dgi_read(rc2dgi_ctx *ctx, int which, const rc2dgi_rect *rect, int format, int flags, void *host,
+                int pitch_bytes);
+int rc2dgi_read_device(rc2dgi_ctx *ctx, int which, const rc2dgi_rect *rect, int format, int flags, void *dev,
+                       int pitch_bytes);
+
 /* cascade resolution (RC2DGI.cs:70-77), JFA step count (RC2DGI.cs:289-292) and which
  * giRT holds the final GI (1 or 2, RC2DGI.cs:365) */
 int rc2dgi_query(rc2dgi_ctx *ctx, int *cascade_w, int *cascade_h, int *jfa_steps, int *final_gi);
@@ -499,7 +541,7 @@ int rc2dgi_set_sky_table(rc2dgi_ctx *ctx, const float *rgb, int n);
  *                     starting when the upper tiles under its footprint are written (2: unrolled march);
  *                     4: the top level in that launch too; f32 cascades, one process.  A wait that times out
  *                     makes the next rc2dgi_sync / rc2dgi_download / rc2dgi_download_level / rc2dgi_compose /
- *                     rc2dgi_reduce / rc2dgi_compose_tone / rc2dgi_histogram / rc2dgi_do / rc2dgi_do_phase return
+ *                     rc2dgi_reduce / rc2dgi_compose_tone / rc2dgi_histogram / rc2dgi_read / rc2dgi_do / rc2dgi_do_phase return
  *                     RC2DGI_E_DEVICE and turns the chain off for the context
  *                     (never a silent wrong frame)
  *   "rc_chain_spin"   diagnostic: polls per chain wait (0: the default bound; -1: every wait times out at once)

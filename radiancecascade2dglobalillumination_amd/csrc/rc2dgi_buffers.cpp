@@ -62,7 +62,7 @@ bool chain_active(const rc2dgi_ctx *c) {
 
 // A chained frame whose workgroup stopped waiting for its upper tiles merged texels that were not written: no
 // silent wrong frame.  The kernel sets a host-mapped word; the next rc2dgi_sync / rc2dgi_download /
-// rc2dgi_download_level / rc2dgi_compose / rc2dgi_reduce / rc2dgi_compose_tone / rc2dgi_histogram / rc2dgi_do /
+// rc2dgi_download_level / rc2dgi_compose / rc2dgi_reduce / rc2dgi_compose_tone / rc2dgi_histogram / rc2dgi_read / rc2dgi_do /
 // rc2dgi_do_phase returns RC2DGI_E_DEVICE and the context
 // falls back to one launch per level from then on.
 int check_chain(rc2dgi_ctx *c) {
@@ -89,6 +89,8 @@ void free_buffers(rc2dgi_ctx *c) {
   c->reduce_buf = nullptr;
   if (c->hist_buf) (void)hipFree(c->hist_buf);
   c->hist_buf = nullptr;
+  if (c->read_buf) (void)hipFree(c->read_buf);
+  c->read_buf = nullptr;
   void *bufs[] = {c->color_in, c->emissive, c->temp, c->color_out, c->jump1, c->jump2, c->dist, c->occ,
                   c->gi1,      c->gi2,      c->blur, c->dirs,      c->sky, c->gi_spare, c->dist_t, c->dist_p, c->dist_n, c->shade,
                   c->cmin,     c->dexit, c->hitc, c->dclr, c->dboxes, c->mfield, c->cell_pal, c->shade_list, c->jtail,

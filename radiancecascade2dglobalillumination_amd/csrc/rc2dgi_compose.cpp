@@ -3,7 +3,8 @@
 // queries too (rc2dgi_sample / rc2dgi_raycast, rc2dgi_query.hip): a point sample resolves its texture as a view does,
 // and so do the region statistics (rc2dgi_reduce, rc2dgi_reduce.hip), whose rectangles are planned here.  Last the
 // edge tables: the tone curves of the views (rc2dgi_set_curve / rc2dgi_compose_tone, rc2dgi_tone.hip) and the
-// histograms of rectangles (rc2dgi_histogram, rc2dgi_hist.hip), planned as the reductions are.
+// histograms of rectangles (rc2dgi_histogram, rc2dgi_hist.hip), planned as the reductions are -- and a rectangle read as
+// an image (rc2dgi_read, rc2dgi_read.hip), staged through a bounded buffer for the host.
 #include "rc2dgi_ctx.h"
 
 #include <cstddef>
@@ -470,6 +471,43 @@ int hist_args(rc2dgi_ctx *c, int which, int channel, const rc2dgi_rect *rects, i
   return RC2DGI_OK;
 }
 
+// ---- a rectangle as an image (rc2dgi_read.hip)
+
+// The checks the two calls share, in the header's order; r becomes the rectangle (the whole texture for null) and
+// *pitch_bytes the tight row where it is 0.  A device destination and its pitch are multiples of a pixel; a host
+// destination may be anything.
+int read_args(rc2dgi_ctx *c, int which, const rc2dgi_rect *rect, int format, int flags, const void *dst,
+              int *pitch_bytes, bool device, TexSource &t, rc2dgi_rect &r) {
+  if (!c) return RC2DGI_E_ARG;
+  RC2DGI_USABLE(c);
+  if (!dst) return fail(c, RC2DGI_E_ARG, "read: null argument");
+  if (int rc = resolve_texture(c, which, RC2DGI_FILTER_POINT, "read: ", t)) return rc;
+  if (format != RC2DGI_FMT_RGBA8 && format != RC2DGI_FMT_RGBA32F && format != RC2DGI_FMT_RGBA16F)
+    return fail(c, RC2DGI_E_ARG, "read: bad format");
+  if (flags & ~RC2DGI_READ_FLIP) return fail(c, RC2DGI_E_ARG, "read: the only flag is RC2DGI_READ_FLIP");
+  r = rect ? *rect : rc2dgi_rect{0, 0, t.nx, t.ny};
+  if (!rect_valid(r, t.nx, t.ny))
+    return fail(c, RC2DGI_E_ARG, "read: the rectangle does not lie inside the texture (no wrap, no clipping)");
+  const int pxb = read_pixel_bytes(format), row = r.w * pxb;  // (w <= 32768)
+  if (*pitch_bytes == 0) *pitch_bytes = row;
+  if (*pitch_bytes < row) return fail(c, RC2DGI_E_ARG, "read: pitch smaller than a row");
+  if (device && (!aligned_to(dst, (uintptr_t)pxb) || *pitch_bytes % pxb != 0))
+    return fail(c, RC2DGI_E_ARG, "read: the destination and the pitch are multiples of a pixel (16 / 8 / 4 bytes)");
+  if (c->world > 1)
+    return fail(c, RC2DGI_E_UNSUPPORTED, "a row-strip shard's textures hold windows and bands: read on an unsharded context");
+  return RC2DGI_OK;
+}
+
+// image rows [j0, j0 + rows) of rectangle r into dst (the first of them at dst), enqueued on the context stream
+int read_enqueue(rc2dgi_ctx *c, const TexSource &t, const rc2dgi_rect &r, int format, int flags, int j0, int rows,
+                 void *dst, size_t pitch) {
+  const bool flip = (flags & RC2DGI_READ_FLIP) != 0;
+  const ReadArgs a{r.x, r.w, flip ? r.y + r.h - 1 - j0 : r.y + j0, flip ? -1 : 1, rows,
+                   static_cast<unsigned char *>(dst), pitch};
+  HIPCHK(c, launch_read(t, a, format, c->stream));
+  return RC2DGI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -573,6 +611,39 @@ int rc2dgi_histogram(rc2dgi_ctx *c, int which, int channel, const rc2dgi_rect *r
   if (int rc = query_buffer(c, c->query_out, c->query_out_cap, bytes)) return rc;
   if (int rc = hist_enqueue(c, t, channel, rects, n, edges, m, c->query_out)) return rc;
   HIPCHK(c, hipMemcpyAsync(counts, c->query_out, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RC2DGI_OK;
+}
+
+// ---- a rectangle as an image (rc2dgi_read.hip)
+int rc2dgi_read_device(rc2dgi_ctx *c, int which, const rc2dgi_rect *rect, int format, int flags, void *dev,
+                       int pitch_bytes) {
+  TexSource t{};
+  rc2dgi_rect r{};
+  if (int rc = read_args(c, which, rect, format, flags, dev, &pitch_bytes, true, t, r)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return read_enqueue(c, t, r, format, flags, 0, r.h, dev, (size_t)pitch_bytes);
+}
+
+int rc2dgi_read(rc2dgi_ctx *c, int which, const rc2dgi_rect *rect, int format, int flags, void *host, int pitch_bytes) {
+  TexSource t{};
+  rc2dgi_rect r{};
+  if (int rc = read_args(c, which, rect, format, flags, host, &pitch_bytes, false, t, r)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = check_chain(c)) return rc;
+  // Staged rows are whole 16-byte lines (every segment a dwordx4), and a block is as many of them as the buffer holds.
+  // The blocks follow each other on the stream: a block's kernel runs when the copy of the one before has read the buffer.
+  const size_t row = (size_t)r.w * read_pixel_bytes(format), spitch = (row + 15) / 16 * 16;
+  static_assert(kReadChunkBytes >= (size_t)32768 * 16, "a row of the widest texture fits the buffer: a block is >= 1 row");
+  const int block = (int)std::min<size_t>(kReadChunkBytes / spitch, (size_t)r.h);
+  if (!c->read_buf) HIPCHK(c, alloc(&c->read_buf, kReadChunkBytes));
+  for (int j0 = 0; j0 < r.h; j0 += block) {
+    const int rows = std::min(block, r.h - j0);
+    if (int rc = read_enqueue(c, t, r, format, flags, j0, rows, c->read_buf, spitch)) return rc;
+    HIPCHK(c, hipMemcpy2DAsync(static_cast<unsigned char *>(host) + (size_t)j0 * (size_t)pitch_bytes, (size_t)pitch_bytes,
+                               c->read_buf, spitch, row, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RC2DGI_OK;
 }

@@ -1,6 +1,6 @@
 // rc2dgi_ctx.h -- the context behind the C ABI (include/rc2dgi.h) and the helpers its host units share:
 // rc2dgi_buffers.cpp (sizes, allocation, tables), rc2dgi_frame.cpp (the frame), rc2dgi_group.cpp (RCCL, sharded
-// groups), rc2dgi_autotune.cpp, rc2dgi_compose.cpp (the display frame, the queries, the region statistics, tone curves and histograms) and rc2dgi_capi.cpp (everything
+// groups), rc2dgi_autotune.cpp, rc2dgi_compose.cpp (the display frame, the queries, the region statistics, tone curves, histograms and image reads) and rc2dgi_capi.cpp (everything
 // else of the ABI).
 #pragma once
 #include "../../include/rc2dgi.h"
@@ -25,6 +25,7 @@
 #include "rc2dgi_query.h"
 #include "rc2dgi_reduce.h"
 #include "rc2dgi_hist.h"
+#include "rc2dgi_read.h"
 #include "rc2dgi_tone.h"
 #include "rc2dgi_shard.h"
 #include "rc2dgi_tuning.h"
@@ -125,6 +126,8 @@ struct rc2dgi_ctx : rc2dgi::Tuning {
                                         // fixed size (reduce_bytes, rc2dgi_compose.cpp), allocated at the first call
   unsigned char *hist_buf = nullptr;    // rc2dgi_histogram's search tree of the edges, then one batch of work items:
                                         // a fixed size (hist_bytes, rc2dgi_compose.cpp), allocated at the first call
+  unsigned char *read_buf = nullptr;    // rc2dgi_read's staged image rows: kReadChunkBytes (rc2dgi_read.h), allocated
+                                        // at the first call
   std::vector<float> curve_host[RC2DGI_MAX_CURVES];  // rc2dgi_set_curve: slot s at [s - 1], 255 edges; empty: not set
   float *curves_dev = nullptr;          // the same as search trees (rc2dgi_tone.h), 256 words a slot; stored on the
                                         // context stream, allocated at the first rc2dgi_set_curve, kept to the end

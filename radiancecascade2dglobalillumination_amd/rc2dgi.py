@@ -31,6 +31,9 @@ RT = {"color": 0, "emissive": 1, "jump1": 2, "jump2": 3, "dist": 4, "gi1": 5, "g
       "final_gi": 9}
 SCREEN_RTS = ("color", "emissive", "jump1", "jump2", "dist", "temp")
 FMT_RGBA8, FMT_RGBA32F = 0, 1
+FMT_RGBA16F = 2  # IEEE binary16, round to nearest even: read / read_into only (upload and download refuse it)
+READ_FLIP = 1    # rc2dgi_read: image row 0 is the rectangle's top row
+_READ_FORMATS = {"float32": FMT_RGBA32F, "float16": FMT_RGBA16F, "uint8": FMT_RGBA8}  # by numpy / torch dtype name
 STATUS = {0: "OK", -1: "E_ARG", -2: "E_UNIFORM", -3: "E_HIP", -4: "E_OOM", -5: "E_UNSUPPORTED", -6: "E_STATE", -7: "E_DEVICE"}
 PASS_NAMES = ("screenuv", "jfa", "rc", "blur", "merge", "total")
 
@@ -271,6 +274,8 @@ def load_library(path: Optional[str] = None):
         "rc2dgi_histogram": ([vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, fp, ctypes.c_int, vp], ctypes.c_int),
         "rc2dgi_histogram_device": ([vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, fp, ctypes.c_int, vp],
                                     ctypes.c_int),
+        "rc2dgi_read": ([vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int], ctypes.c_int),
+        "rc2dgi_read_device": ([vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -656,6 +661,50 @@ class RC2DGI:
             raise ValueError(f"histogram_into: expected shape ({a.shape[0]}, {e.size + 4}), got {tuple(dst.shape)}")
         self._check(self._L.rc2dgi_histogram_device(self._h, w, ch, a.ctypes.data_as(ctypes.c_void_p), a.shape[0], ep,
                                                     e.size, ctypes.c_void_p(dst.data_ptr())), "histogram_into")
+
+    # ---------------------------------------------------------------- a rectangle as an image
+    def _read_rect(self, which, rect):
+        w = RT[which] if isinstance(which, str) else int(which)
+        if rect is None:
+            return w, None, self.texture_size(w)
+        r = _rect_array([rect])
+        return w, r, (int(r[0]["w"]), int(r[0]["h"]))
+
+    def read(self, which, rect=None, dtype=np.float32, flip=False) -> np.ndarray:
+        """A rectangle of a render texture as an (h, w, 4) image converted on the GPU (rc2dgi_read): which -- a name of
+        RT or an rc2dgi_rt id; rect -- (x, y, w, h) in texels of that texture, GL order (row 0 = the bottom), None: the
+        whole texture; dtype -- np.float32 (the values download returns), np.float16 (round to nearest even, as
+        astype(np.float16)) or np.uint8 (q8, the bytes download returns); flip -- image row 0 is the rectangle's top
+        row, the order compose writes.  Synchronous."""
+        fmt = _READ_FORMATS.get(np.dtype(dtype).name)
+        if fmt is None:
+            raise TypeError("read: dtype is float32, float16 or uint8")
+        w, r, (rw, rh) = self._read_rect(which, rect)
+        tw, th = self.texture_size(w)
+        if not (0 < rw <= tw and 0 < rh <= th):
+            rw = rh = 1  # (the library refuses the rectangle: no image of its size is made first)
+        out = np.empty((rh, rw, 4), dtype)
+        self._check(self._L.rc2dgi_read(self._h, w, None if r is None else r.ctypes.data_as(ctypes.c_void_p), fmt,
+                                        READ_FLIP if flip else 0, out.ctypes.data_as(ctypes.c_void_p), 0), "read")
+        return out
+
+    def read_into(self, dst, which, rect=None, flip=False) -> None:
+        """The same image into device memory, enqueued on the context stream after whatever frame is in flight
+        (rc2dgi_read_device; sync() or order the stream before reading, as with compose_into).  dst: a torch tensor
+        (h, w, 4) on this context's GPU with contiguous pixels; its dtype float32 / float16 / uint8 selects the format,
+        its row stride the pitch (rows may be padded; the padding is not written)."""
+        if not getattr(dst, "is_cuda", False) or dst.device.index != self.device:
+            raise TypeError("read_into: expected a tensor on this context's GPU")
+        fmt = _READ_FORMATS.get(str(dst.dtype).replace("torch.", ""))
+        if fmt is None:
+            raise TypeError("read_into: expected a float32, float16 or uint8 tensor")
+        w, r, (rw, rh) = self._read_rect(which, rect)
+        if dst.dim() != 3 or tuple(dst.shape) != (rh, rw, 4) or dst.stride(2) != 1 or dst.stride(1) != 4:
+            raise ValueError(f"read_into: expected shape ({rh}, {rw}, 4) with contiguous pixels, got {tuple(dst.shape)}")
+        pitch = int(dst.stride(0)) * dst.element_size() if rh > 1 else 0
+        self._check(self._L.rc2dgi_read_device(self._h, w, None if r is None else r.ctypes.data_as(ctypes.c_void_p), fmt,
+                                               READ_FLIP if flip else 0, ctypes.c_void_p(dst.data_ptr()), pitch),
+                    "read_into")
 
     def set_tuning(self, key: str, value: int) -> None:
         """Performance knobs (results are identical for every value), e.g. rc_variant."""
