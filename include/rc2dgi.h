@@ -104,10 +104,19 @@ typedef enum rc2dgi_format {
 } rc2dgi_format;
 
 typedef struct rc2dgi_config {
-  int screen_width;        /* screenWidth  (RC2DGI.cs:7) */
-  int screen_height;       /* screenHeight (RC2DGI.cs:8) */
-  int cascade_count;       /* cascadeCount (RC2DGI.cs:66), 1..15 */
-  float render_scale;      /* renderScale  (RC2DGI.cs:67), > 0 */
+  int screen_width;        /* screenWidth  (RC2DGI.cs:7), 1..32768.  Verified against the CPU oracle, bit for bit: an axis
+                              up to 32768 on screens a few texels thin (32768 x 8, 8 x 32768, 16 x 32768, 20000 x 12 ...),
+                              squares up to 2048^2 over the whole frame, 4096^2 pass by pass; larger squares are admitted
+                              and not verified against it */
+  int screen_height;       /* screenHeight (RC2DGI.cs:8), 1..32768 */
+  int cascade_count;       /* cascadeCount (RC2DGI.cs:66), 1..15.  Verified: 1..12.  13, 14 and 15 are admitted and NOT
+                              verified: they need cascades of at least 8192^2, 16384^2, 32768^2 and tables of 4^N entries
+                              (N = 15: 8 GiB of directions, 16 GiB of sky), and from N = 13 on (float)((1 << 2N) - 1), the
+                              denominator of the ray intervals, is no longer exact in fp32 */
+  float render_scale;      /* renderScale  (RC2DGI.cs:67), > 0, with (float)screen_width * render_scale and
+                              (float)screen_height * render_scale <= 32768: the cascade textures (that size rounded up
+                              to a multiple of 2^cascade_count) hold at most 32768 texels per axis, whatever the cascade
+                              count.  Anything larger is RC2DGI_E_ARG from rc2dgi_create */
   float ray_range;         /* rayRange     (RC2DGI.cs:68) -> _RayRange */
   int storage;             /* rc2dgi_storage */
   int device;              /* HIP device ordinal */

@@ -227,6 +227,15 @@ static void circ_band(const RowSet &r, int &b0, int &bn) {
   bn = r.n - gap;
 }
 
+// Rows giRT1 / giRT2 are allocated with.  k_rc_level stages the upper level's footprint of a tile, up to 18 rows for
+// the 32-row tiles, with loads that are unconditional and wrap once (REPEAT): on a cascade of fewer rows than the
+// footprint the rows past the second wrap are read (never used: they lie under probes the tile does not have) at
+// row indices below the footprint's height.  The textures keep that many rows allocated, so those loads stay inside
+// them (cascades of 8 rows: 32768 x 8 at cascade_count 3 with the 32-row tiles).  Columns wrap into the pitch padding.
+// (gi_spare trades places with them only after a fused blur, which takes cascades of 16 rows and more: there the
+// highest row read, 15, exists.)
+static size_t gi_alloc_rows(size_t rows) { return std::max(rows, (size_t)18); }
+
 // giRT1 / giRT2 for this frame's plan: the bands of the levels each one receives (level L: giRT1 when N-1-L is even,
 // phase2_levels), or whole.  Before anything of the frame is enqueued (out_buffers).
 static int gi_buffers(rc2dgi_ctx *c) {
@@ -256,8 +265,8 @@ static int gi_buffers(rc2dgi_ctx *c) {
   }
   c->gi_rows[0] = c->gi_rows[1] = 0;
   c->gband = false;
-  HIPCHK(c, alloc(&c->gi1, rows[0] * c->cd.pitch * gi_bytes(c)));
-  HIPCHK(c, alloc(&c->gi2, rows[1] * c->cd.pitch * gi_bytes(c)));
+  HIPCHK(c, alloc(&c->gi1, gi_alloc_rows(rows[0]) * c->cd.pitch * gi_bytes(c)));
+  HIPCHK(c, alloc(&c->gi2, gi_alloc_rows(rows[1]) * c->cd.pitch * gi_bytes(c)));
   c->gi_rows[0] = rows[0];
   c->gi_rows[1] = rows[1];
   c->gband = gb;
@@ -309,8 +318,8 @@ int prepare_side_buffers(rc2dgi_ctx *c, bool all) {
     packed |= rc_variant_packed(v);
     nib |= rc_variant_nib(v);
   }
-  // (the packed marches run on power-of-two screens of up to 16384 columns only)
-  const bool p2s = c->sd.powW && c->sd.powH && c->cd.powW && c->cd.powH && c->W <= 16384;
+  // (the packed marches run on power-of-two screens of up to 16384 columns and rows only)
+  const bool p2s = c->sd.powW && c->sd.powH && c->cd.powW && c->cd.powH && c->W <= 16384 && c->H <= 16384;
   if (tiled && !c->dist_t)
     HIPCHK(c, alloc(&c->dist_t, (size_t)((c->W + 7) / 8) * ((c->H + 7) / 8) * 64 * sizeof(unsigned short)));
   if (packed && p2s && !c->dist_p) HIPCHK(c, alloc(&c->dist_p, dist_packed_bytes(c->W, c->H)));
@@ -408,8 +417,8 @@ int allocate(rc2dgi_ctx *c) {
     HIPCHK(c, hipMemcpy(c->dboxes, boxes.data(), boxes.size() * sizeof(int4), hipMemcpyHostToDevice));
   }
   const size_t gsz = gi_bytes(c);  // giRT1 / giRT2 texel size (storage)
-  HIPCHK(c, alloc(&c->gi1, nc * gsz));
-  HIPCHK(c, alloc(&c->gi2, nc * gsz));
+  HIPCHK(c, alloc(&c->gi1, gi_alloc_rows((size_t)c->CH) * cp * gsz));
+  HIPCHK(c, alloc(&c->gi2, gi_alloc_rows((size_t)c->CH) * cp * gsz));
   c->gi_rows[0] = c->gi_rows[1] = (size_t)c->CH;
   c->gband = false;
   HIPCHK(c, alloc(&c->blur, nc * sizeof(float4)));

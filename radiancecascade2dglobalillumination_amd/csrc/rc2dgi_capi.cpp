@@ -9,6 +9,14 @@ bool screen_rt(int which) {
          which == RC2DGI_RT_JUMP2 || which == RC2DGI_RT_DIST || which == RC2DGI_RT_TEMP;
 }
 
+// The cascade textures stay within the 32768 texels per axis of the screen's: the accessory calls' planners, the
+// read buffer (a row of at most 32768 * 16 bytes) and the workgroup map's 16-bit tile fields are written for that
+// bound, and nothing wider has been run.  derive_sizes rounds W * renderScale up to a multiple of 2^N, and 32768 is
+// one for every N <= 15: the cascade fits exactly when the scaled screen does, whatever the cascade count (so
+// _CascadeCount cannot push it over).  Tested before derive_sizes, whose int sizes a large renderScale would wrap.
+constexpr float kMaxAxis = 32768.0f;
+bool cascade_fits(int W, int H, float rs) { return (float)W * rs <= kMaxAxis && (float)H * rs <= kMaxAxis; }
+
 inline unsigned char to_unorm8(float x) {  // GL readback conversion: clamp, round to nearest even; NaN -> 0 as q8 does
   float v = x > 0.0f ? (x > 1.0f ? 1.0f : x) : 0.0f;  // (a NaN compares false: the rows a strip shard does not hold)
   return (unsigned char)std::nearbyint(v * 255.0f);
@@ -34,6 +42,10 @@ int rc2dgi_create(const rc2dgi_config *cfg, rc2dgi_ctx **out) {
   if (cfg->storage != RC2DGI_STORAGE_F32 && cfg->storage != RC2DGI_STORAGE_F16 &&
       cfg->storage != RC2DGI_STORAGE_RGBA8_COMPAT)
     return RC2DGI_E_ARG;
+  if (!cascade_fits(cfg->screen_width, cfg->screen_height, cfg->render_scale)) {
+    fprintf(stderr, "rc2dgi_create: the cascade resolution exceeds 32768 on an axis\n");
+    return RC2DGI_E_ARG;
+  }
   rc2dgi_ctx *c = new (std::nothrow) rc2dgi_ctx();
   if (!c) return RC2DGI_E_OOM;
   c->device = cfg->device;

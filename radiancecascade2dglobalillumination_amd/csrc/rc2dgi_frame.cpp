@@ -165,9 +165,9 @@ int phase2_side(rc2dgi_ctx *c, SidePass &f) {
     packed |= rc_variant_packed(v);
     nib |= rc_variant_nib(v);
   }
-  // (the packed marches run on power-of-two screens of up to 16384 columns only; elsewhere their variants
-  // launch the plain-field march, and the copies would be built for nothing)
-  const bool p2s = c->sd.powW && c->sd.powH && c->cd.powW && c->cd.powH && c->W <= 16384;
+  // (the packed marches run on power-of-two screens of up to 16384 columns and rows only, the bound jfa_p2_taps
+  // keeps; elsewhere their variants launch the plain-field march, and the copies would be built for nothing)
+  const bool p2s = c->sd.powW && c->sd.powH && c->cd.powW && c->cd.powH && c->W <= 16384 && c->H <= 16384;
   // (the copies were allocated when the schedule was set: prepare_side_buffers; a frame never allocates)
   if ((tiled && !c->dist_t) || (packed && p2s && !c->dist_p) || (nib && p2s && !c->dist_n))
     return fail(c, RC2DGI_E_STATE, "distRT copy of the schedule not prepared");

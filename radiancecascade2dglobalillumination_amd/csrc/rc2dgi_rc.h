@@ -1414,8 +1414,9 @@ static inline int rc_tile_params(const RcLevelArgs &a, RcParams &P) {
 template <int TX, int TY, int PY, int PD = 1, int UNR = 1, int DL = 0, class GI = GiF32>
 static inline hipError_t launch_rc_tiles(const RcLevelArgs &a, RcParams P, hipStream_t st) {
   const bool p2s = P.s.powW && P.s.powH && P.c.powW && P.c.powH;
-  if constexpr (DL == 2 || DL == 3) {  // packed field: power-of-two screens up to 16384 wide; same bits either way
-    if (!p2s || P.s.W > 16384) return launch_rc_tiles<TX, TY, PY, PD, UNR, 0, GI>(a, P, st);
+  if constexpr (DL == 2 || DL == 3) {  // packed field: power-of-two screens up to 16384 on both axes (pack_div14 /
+    // pack_div26 are proved for columns below 16384; rows beyond it were never run); same bits either way
+    if (!p2s || P.s.W > 16384 || P.s.H > 16384) return launch_rc_tiles<TX, TY, PY, PD, UNR, 0, GI>(a, P, st);
     if (!(DL == 2 ? a.dist_packed : a.dist_nib)) return hipErrorInvalidValue;
   }
   const int nwg = rc_tile_params<TX, TY, PY, PD, DL>(a, P);
