@@ -1,7 +1,9 @@
 // rc2dgi_ctx.h -- the context behind the C ABI (include/rc2dgi.h) and the helpers its host units share:
 // rc2dgi_buffers.cpp (sizes, allocation, tables), rc2dgi_frame.cpp (the frame), rc2dgi_group.cpp (RCCL, sharded
-// groups), rc2dgi_autotune.cpp, rc2dgi_compose.cpp (the display frame, the queries, the region statistics, tone curves, histograms and image reads) and rc2dgi_capi.cpp (everything
-// else of the ABI).
+// groups), rc2dgi_autotune.cpp, the accessory calls over rc2dgi_accessory.h -- rc2dgi_display.cpp (the display frame
+// and its tone curves), rc2dgi_regions.cpp (region statistics, histograms and image reads, planned by
+// rc2dgi_rectplan.cpp) and rc2dgi_points.cpp (samples and ray casts) -- and rc2dgi_capi.cpp (everything else of the
+// ABI).
 #pragma once
 #include "../../include/rc2dgi.h"
 
@@ -123,9 +125,9 @@ struct rc2dgi_ctx : rc2dgi::Tuning {
   unsigned char *query_in = nullptr, *query_out = nullptr;  // rc2dgi_sample / rc2dgi_raycast's points or rays and
   size_t query_in_cap = 0, query_out_cap = 0;               // their results, grown on demand
   unsigned char *reduce_buf = nullptr;  // rc2dgi_reduce's plan (work items, joins) and band partials of one batch: a
-                                        // fixed size (reduce_bytes, rc2dgi_compose.cpp), allocated at the first call
+                                        // fixed size (reduce_bytes, rc2dgi_regions.cpp), allocated at the first call
   unsigned char *hist_buf = nullptr;    // rc2dgi_histogram's search tree of the edges, then one batch of work items:
-                                        // a fixed size (hist_bytes, rc2dgi_compose.cpp), allocated at the first call
+                                        // a fixed size (hist_bytes, rc2dgi_regions.cpp), allocated at the first call
   unsigned char *read_buf = nullptr;    // rc2dgi_read's staged image rows: kReadChunkBytes (rc2dgi_read.h), allocated
                                         // at the first call
   std::vector<float> curve_host[RC2DGI_MAX_CURVES];  // rc2dgi_set_curve: slot s at [s - 1], 255 edges; empty: not set

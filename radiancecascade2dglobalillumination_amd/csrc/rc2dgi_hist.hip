@@ -5,10 +5,10 @@
 // argument, and why this kernel may use atomics where rc2dgi_reduce.hip fixes a tree: integer atomics only, in LDS and
 // in global memory, and no float is accumulated anywhere.
 //
-// k_hist: one WORKGROUP per work item (a rectangle and a block of its rows, cut on the host into 2048 to 16384
-// texels, hist_block_rows).  It stages the search tree of the edges in LDS (rc2dgi_tone.h: level order, so that the
-// lanes' unrelated probes of a level fall on distinct banks) and keeps the record's m + 2 counters there: word 0 is
-// `nan`, word 1 + b is bin b, the order of the record from its third word on.  A lane takes four consecutive texels of
+// k_hist: one WORKGROUP per work item (a rectangle and a block of its rows, 2048 to 16384 texels: hist_block_rows,
+// rc2dgi_rectplan.cpp; the item is rc2dgi_rects.h's, derived here from an inline descriptor or on the host).  It
+// stages the search tree of the edges in LDS (rc2dgi_tone.h: level order, so that the lanes' unrelated probes
+// of a level fall on distinct banks) and keeps the record's m + 2 counters there: word 0 is `nan`, word 1 + b is bin b, the order of the record from its third word on.  A lane takes four consecutive texels of
 // a row, as k_reduce_rows does: rows of more than 1024 texels are walked in chunks, narrow ones are packed 256 / lr
 // rows a pass (lr the power of two >= w / 4 lanes).  The loads are unconditional, at addresses clamped into the block,
 // and the next step's texels are loaded before the current ones are searched.  A texel's scalar is its channel or the
@@ -37,18 +37,6 @@ constexpr int kChunk = 256 * kLeaves;      // texels of a row a workgroup takes 
 struct Leaves {
   float4 p[kLeaves];
 };
-
-__device__ __forceinline__ HistItem inline_item(const HistInline &inl, int k) {
-  HistDesc d = inl.d[0];
-#pragma unroll
-  for (int r = 1; r < kHistInline; ++r)
-    if (r < inl.n && k >= inl.d[r].item0) d = inl.d[r];
-  if (d.w == 0) return HistItem{0, 0, 0, 0, 0, 0, (unsigned)d.out | kHistSingle | kHistFirst};
-  const int b = k - d.item0, r0 = b * d.rows;
-  const int r1 = d.h - r0 < d.rows ? d.h : r0 + d.rows;
-  return HistItem{d.x, d.y, d.w, r0, r1, d.w * d.h,
-                  (unsigned)d.out | (d.rows >= d.h ? kHistSingle : 0u) | (b == 0 ? kHistFirst : 0u)};
-}
 
 // the scalar of a texel (channel is uniform); the luma is five single operations (the unit is built -ffp-contract=off)
 __device__ __forceinline__ float texel_scalar(float4 p, int channel) {
@@ -133,13 +121,19 @@ __device__ __forceinline__ void hist_item(TexSource t, const HistItem &it, int c
   }
 }
 
-__global__ __launch_bounds__(256) void k_hist(const TexSource t, const HistInline inl,
+__global__ __launch_bounds__(256) void k_hist(const TexSource t, const RectInline inl,
                                               const HistItem *__restrict__ items, const HistTable tab,
                                               unsigned *__restrict__ counts) {
   __shared__ float tree[kHistTreeWords];
   __shared__ unsigned bins[kHistTreeWords + 1];  // m + 2 <= 1025 counters
   const int k = (int)blockIdx.x, tid = (int)threadIdx.x;
-  const HistItem it = inl.n > 0 ? inline_item(inl, k) : items[k];  // (k is uniform: scalar loads)
+  HistItem it;  // (k is uniform: scalar loads)
+  if (inl.n > 0) {
+    const RectDesc d = inline_desc(inl, k);
+    it = hist_item_of(d, k - d.item0);
+  } else {
+    it = items[k];
+  }
   unsigned *rec = counts + (size_t)(it.out & 0xFFFFFu) * (size_t)(tab.m + 4);
   if (it.w == 0) {  // an invalid rectangle: no texture memory is read, the other words are zero
     if (tid == 0) rec[0] = (unsigned)RC2DGI_STATS_INVALID;
@@ -173,7 +167,7 @@ __global__ __launch_bounds__(256) void k_hist(const TexSource t, const HistInlin
 
 }  // namespace
 
-hipError_t launch_hist(const TexSource &t, const HistInline &inl, const HistItem *items, int n, const HistTable &tab,
+hipError_t launch_hist(const TexSource &t, const RectInline &inl, const HistItem *items, int n, const HistTable &tab,
                        void *counts, hipStream_t st) {
   hipLaunchKernelGGL(k_hist, dim3((unsigned)n), dim3(256), 0, st, t, inl, items, tab, static_cast<unsigned *>(counts));
   return hipGetLastError();

@@ -21,7 +21,7 @@ enum PresentKind {
   PK_CONST = 7   // (0, 0, 0, 1): giRT2 with one cascade (ClearAllRTs content)
 };
 
-// a render texture resolved on the host (resolve_texture, rc2dgi_compose.cpp): the source in its stored format, as
+// a render texture resolved on the host (resolve_texture, rc2dgi_accessory.h): the source in its stored format, as
 // rc2dgi_download reads it.  What k_present fetches for a view and k_sample (rc2dgi_query.hip) for a point; the
 // decoder of both is rc2dgi_texel.h.
 struct TexSource {

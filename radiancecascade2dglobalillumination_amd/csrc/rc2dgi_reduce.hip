@@ -6,7 +6,7 @@
 // a + b == b + a hold for every partial: padding can be skipped and operands swapped.  Two kernels, no atomics, no
 // wait between workgroups.
 //
-// k_reduce_rows: one WAVE per work item (a rectangle and a band of its rows, cut on the host; the four waves of a
+// k_reduce_rows: one WAVE per work item (a rectangle and a band of its rows, rc2dgi_rects.h; the four waves of a
 // workgroup are independent, no LDS).  A lane holds kReduceLeaves = 4 consecutive leaves of a row and adds them as
 // (l0 + l1) + (l2 + l3), the tree's two lowest levels.  The next six are the DPP wave reduction (row_shr 1, 2, 4, 8,
 // row_bcast15, row_bcast31): lane i with i % 2^k == 2^k - 1 takes s[i - 2^(k-1)] + s[i], the adjacent-pair tree
@@ -21,8 +21,9 @@
 // Row (or row-group) sums combine by a second such stack.  The next step's texels are loaded before the current ones are
 // reduced.  min / max stay lane-local to the end of the item, counts are the population of the compare mask (their
 // order is free).  A step whose values are all finite and present, the common one, takes a form without selects.
-// The plan is the host's list of items, or for a call of up to kReduceInline rectangles (the whole texture, one
-// sprite) a few descriptors in the kernel's arguments, from which a wave derives its item: nothing is uploaded then.
+// The plan is the host's list of items, or for a call of up to kRectInline rectangles (the whole texture, one
+// sprite) a few descriptors in the kernel's arguments, from which a wave derives its item by the functions the host
+// fills its list with (rc2dgi_rects.h): nothing is uploaded then.
 //
 // k_reduce_bands: one wave per rectangle of more than one band, lane l on band partials 512 c + 8 l .. + 7 (loaded
 // together, added by the pair tree), then the same wave tree and stack.
@@ -203,23 +204,6 @@ struct Leaves {
   float4 p[kReduceLeaves];
 };
 
-// the descriptor of the rectangle item k belongs to (static indices: the argument block stays in scalar registers)
-__device__ __forceinline__ ReduceDesc inline_desc(const ReduceInline &inl, int k) {
-  ReduceDesc d = inl.d[0];
-#pragma unroll
-  for (int r = 1; r < kReduceInline; ++r)
-    if (r < inl.n && k >= inl.d[r].item0) d = inl.d[r];
-  return d;
-}
-
-__device__ __forceinline__ ReduceItem inline_item(const ReduceInline &inl, int k) {
-  const ReduceDesc d = inline_desc(inl, k);
-  if (d.w == 0) return ReduceItem{0, 0, 0, 0, 0, (unsigned)d.out | kReduceFinal};
-  const int b = k - d.item0, r0 = b * d.rw;
-  const int r1 = d.h - r0 < d.rw ? d.h : r0 + d.rw;
-  return ReduceItem{d.x, d.y, d.w, r0, r1, d.rw >= d.h ? (unsigned)d.out | kReduceFinal : (unsigned)(d.part0 + b)};
-}
-
 // One item of a texture whose storage kind is the constant KIND: present_texel's switch folds to one case, the loop
 // carries no branch on it.
 template <int KIND>
@@ -322,14 +306,20 @@ __device__ __forceinline__ void reduce_item(TexSource t, const ReduceItem &it, i
   }
 }
 
-__global__ __launch_bounds__(256) void k_reduce_rows(const TexSource t, const ReduceInline inl,
+__global__ __launch_bounds__(256) void k_reduce_rows(const TexSource t, const RectInline inl,
                                                      const ReduceItem *__restrict__ items, int n,
                                                      ReducePartial *__restrict__ partials,
                                                      rc2dgi_stats *__restrict__ stats) {
   const int lane = (int)(threadIdx.x & 63u);
   const int k = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
   if (k >= n) return;
-  const ReduceItem it = inl.n > 0 ? inline_item(inl, k) : items[k];  // (k is wave-uniform: scalar loads)
+  ReduceItem it;  // (k is wave-uniform: scalar loads)
+  if (inl.n > 0) {
+    const RectDesc d = inline_desc(inl, k);
+    it = reduce_item_of(d, k - d.item0);
+  } else {
+    it = items[k];
+  }
   if (it.w == 0) {  // an invalid rectangle: no texture memory is read
     if (lane == 63) {
       rc2dgi_stats *o = stats + (it.out & ~kReduceFinal);
@@ -357,7 +347,7 @@ __global__ __launch_bounds__(256) void k_reduce_rows(const TexSource t, const Re
   }
 }
 
-__global__ __launch_bounds__(256) void k_reduce_bands(const ReduceInline inl, const ReduceJoin *__restrict__ joins, int n,
+__global__ __launch_bounds__(256) void k_reduce_bands(const RectInline inl, const ReduceJoin *__restrict__ joins, int n,
                                                       const ReducePartial *__restrict__ partials,
                                                       rc2dgi_stats *__restrict__ stats) {
   const int lane = (int)(threadIdx.x & 63u);
@@ -365,12 +355,12 @@ __global__ __launch_bounds__(256) void k_reduce_bands(const ReduceInline inl, co
   if (k >= n) return;
   ReduceJoin j;
   if (inl.n > 0) {  // rectangle k of the inline plan, if it has more than one band
-    ReduceDesc d = inl.d[0];
+    RectDesc d = inl.d[0];
 #pragma unroll
-    for (int r = 1; r < kReduceInline; ++r)
+    for (int r = 1; r < kRectInline; ++r)
       if (r == k) d = inl.d[r];
-    if (d.w == 0 || d.rw >= d.h) return;
-    j = ReduceJoin{d.part0, (int)(((long long)d.h + d.rw - 1) >> __builtin_ctz((unsigned)d.rw)), d.out, d.w * d.h};
+    if (d.w == 0 || d.rows >= d.h) return;
+    j = reduce_join_of(d);
   } else {
     j = joins[k];
   }
@@ -412,14 +402,14 @@ __global__ __launch_bounds__(256) void k_reduce_bands(const ReduceInline inl, co
 
 }  // namespace
 
-hipError_t launch_reduce_rows(const TexSource &t, const ReduceInline &inl, const ReduceItem *items, int n,
+hipError_t launch_reduce_rows(const TexSource &t, const RectInline &inl, const ReduceItem *items, int n,
                               ReducePartial *partials, void *stats, hipStream_t st) {
   hipLaunchKernelGGL(k_reduce_rows, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, t, inl, items, n, partials,
                      static_cast<rc2dgi_stats *>(stats));
   return hipGetLastError();
 }
 
-hipError_t launch_reduce_bands(const ReduceInline &inl, const ReduceJoin *joins, int n, const ReducePartial *partials,
+hipError_t launch_reduce_bands(const RectInline &inl, const ReduceJoin *joins, int n, const ReducePartial *partials,
                                void *stats, hipStream_t st) {
   hipLaunchKernelGGL(k_reduce_bands, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, inl, joins, n, partials,
                      static_cast<rc2dgi_stats *>(stats));

@@ -296,6 +296,75 @@ def test_sprites_across_a_batch_boundary(R, ref_lib, big):
     both_variants(R, ctx, rects, want, "sprites over three batches")
 
 
+# ------------------------------------------------------------------ 2c: the inline plan against the uploaded one
+# A call of up to four rectangles carries descriptors in the kernels' arguments and the device derives its work items
+# (csrc/rc2dgi_rects.h); a longer one uploads the items the host derives from the same descriptors.  The rectangles are
+# the smallest at which each path of the cut is live: narrow rows in three bands of 16 rows, the last one short (five
+# histogram blocks of 8 rows); wide rows in three bands of 8 rows; rows of more than 1024 texels in three histogram
+# blocks of 2 rows; and an invalid rectangle, x + w one past the edge.
+PLAN_SCREEN = (1040, 48)
+PLAN_RECTS = [[1, 3, 256, 40], [700, 11, 257, 20], [7, 40, 1025, 5], [1031, 0, 10, 5]]
+PLAN_FIFTH = [[0, 0, 1, 1]]
+
+
+def build_rect_plan(tmp_path_factory):
+    """csrc/rc2dgi_rectplan.cpp, the host's planner (no part of the ABI: found by its C++ names), as a ctypes library:
+    reduce_band_rows(w, h) and hist_block_rows(w, h)."""
+    import os
+    import subprocess
+
+    from radiancecascade2dglobalillumination_amd import _build
+
+    so = str(tmp_path_factory.mktemp("rectplan") / "librectplan.so")
+    subprocess.run([_build.hipcc(), "-O1", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(_build.ROOT, "include"),
+                    "-o", so, os.path.join(_build.CSRC, "rc2dgi_rectplan.cpp")], check=True)
+    L = ctypes.CDLL(so)
+    for name, sym in (("reduce_band_rows", "_ZN6rc2dgi16reduce_band_rowsEii"),
+                      ("hist_block_rows", "_ZN6rc2dgi15hist_block_rowsEii")):
+        f = getattr(L, sym)
+        f.argtypes, f.restype = [ctypes.c_int, ctypes.c_int], ctypes.c_int
+        setattr(L, name, f)
+    return L
+
+
+def planned(rows_of, rect):
+    """(rows a band or block, bands or blocks) of a rectangle"""
+    rows = rows_of(rect[2], rect[3])
+    return rows, -(-rect[3] // rows)
+
+
+def plan_context(R):
+    """f32, two cascades, no frame: COLOR is a random finite upload with a few NaN / inf texels inside the rectangles"""
+    W, H = PLAN_SCREEN
+    ctx = R.RC2DGI(W, H, cascade_count=2, storage="f32")
+    v = gpu_texture(W, H, False).copy()
+    for (y, x, ch), bits in zip([(5, 10, 0), (20, 200, 1), (42, 255, 2), (15, 800, 2), (30, 956, 3), (41, 500, 3),
+                                 (44, 1031, 0), (0, 0, 1)],
+                                [0x7FC00000, 0x7F800000, 0xFF800000, 0xFFC00001, 0x7F800000, 0x7FC00000, 0xFF800000, 0x7FC00000]):
+        v[y, x, ch] = np.uint32(bits).view(f32)
+    ctx.upload("color", v)
+    tex = ctx.download("color")
+    assert np.array_equal(tex.view(np.uint32), v.view(np.uint32)), "an f32 upload is stored as it is"
+    return ctx, tex
+
+
+def test_inline_and_uploaded_plans_give_the_same_records(R, ref_lib, tmp_path_factory):
+    plan = build_rect_plan(tmp_path_factory)
+    assert planned(plan.reduce_band_rows, PLAN_RECTS[0]) == (16, 3), "narrow rows: three bands, the last one short"
+    assert planned(plan.reduce_band_rows, PLAN_RECTS[1]) == (8, 3), "wide rows: three bands"
+    ctx, tex = plan_context(R)
+    want = ref_reduce(ref_lib, tex, PLAN_RECTS + PLAN_FIFTH)
+    assert want["status"].tolist() == [0, 0, 0, -1, 0] and (want["nonfinite"][:3].sum(1) > 0).all()
+    four = ctx.reduce("color", PLAN_RECTS)                 # n = 4: the inline plan
+    five = ctx.reduce("color", PLAN_RECTS + PLAN_FIFTH)    # n = 5: the uploaded plan
+    same(four, want[:4], "the inline plan against the reference", PLAN_RECTS)
+    same(five, want, "the uploaded plan against the reference", PLAN_RECTS + PLAN_FIFTH)
+    assert four.tobytes() == five[:4].tobytes(), "records 0 .. 3 of the two plans"
+    both_variants(R, ctx, np.int32(PLAN_RECTS), want[:4], "the inline plan")
+    both_variants(R, ctx, np.int32(PLAN_RECTS + PLAN_FIFTH), want, "the uploaded plan")
+    ctx.close()
+
+
 # ------------------------------------------------------------------ 3: many small rectangles
 def sprite_rects(n, tw, th, seed):
     """n random rectangles with w, h in 1 .. 40 inside tw x th, 5 % of them invalid in one of the ways there are"""

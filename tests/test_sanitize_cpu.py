@@ -2,7 +2,9 @@
 (oracle/rc2dgi_oracle.c: whole frames in every mode plus row-restricted passes) and the row-strip
 planner (csrc/rc2dgi_shard.cpp: plan_frame and the JumpFlood exchange over many sizes and shard
 counts, with its invariants checked) and the tuning knob table (csrc/rc2dgi_tuning.cpp against a restatement
-of the header's contract, tests/sanitize/tuning_check.cpp), built by tests/sanitize/Makefile with
+of the header's contract, tests/sanitize/tuning_check.cpp) and the planner of the rectangle calls and of a view's
+clip (csrc/rc2dgi_rectplan.cpp with the cut csrc/rc2dgi_rects.h shares with the kernels, its invariants checked by
+tests/sanitize/rects_check.cpp), built by tests/sanitize/Makefile with
 -fsanitize=address,undefined (UB fatal).  GPU sanitizers are not available on this pool."""
 import os
 import shutil
@@ -22,7 +24,7 @@ def built():
     subprocess.run(["make", "-s", "-C", HERE], check=True)
 
 
-@pytest.mark.parametrize("exe", ["oracle_asan", "plan_asan", "tuning_check"])
+@pytest.mark.parametrize("exe", ["oracle_asan", "plan_asan", "tuning_check", "rects_check"])
 def test_sanitized_run_is_clean(built, exe):
     r = subprocess.run([os.path.join(HERE, exe)], capture_output=True, text=True, env=ENV, timeout=600)
     report = r.stdout[-2000:] + r.stderr[-4000:]

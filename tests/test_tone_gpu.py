@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from test_reduce_cpu import gpu_texture
-from test_reduce_gpu import demo_context, sprite_rects
+from test_reduce_gpu import PLAN_FIFTH, PLAN_RECTS, build_rect_plan, demo_context, plan_context, planned, sprite_rects
 from test_tone_cpu import INVALID, build_tone_ref, log_table, ref_compose, ref_hist, tone_curves
 
 pytestmark = pytest.mark.gpu
@@ -385,6 +385,25 @@ def test_many_workgroups_feed_one_record(R, ref_lib, big, table):
     ctx, tex = big
     pick = [t for t in tables_for(tex) if t[0] == table]
     check_hist(ctx, ref_lib, tex, big_rects(), "2051 x 1030", pick)
+
+
+def test_inline_and_uploaded_plans_give_the_same_records(R, ref_lib, tmp_path_factory):
+    """tests/test_reduce_gpu.py's rectangles (section 2c there): a call of four takes the plan in the kernel's
+    arguments, a call of five the uploaded one."""
+    plan = build_rect_plan(tmp_path_factory)
+    assert planned(plan.hist_block_rows, PLAN_RECTS[0]) == (8, 5), "narrow rows: five blocks"
+    assert planned(plan.hist_block_rows, PLAN_RECTS[2]) == (2, 3), "rows of more than 1024 texels: three blocks"
+    ctx, tex = plan_context(R)
+    rects5 = PLAN_RECTS + PLAN_FIFTH
+    for tname, edges, ch in tables_for(tex):
+        want = ref_hist(ref_lib, tex, CHANNELS.index(ch), rects5, edges)
+        assert want[:, 0].tolist() == [0, 0, 0, INVALID, 0]
+        four = ctx.histogram("color", edges, ch, PLAN_RECTS)   # n = 4: the inline plan
+        five = ctx.histogram("color", edges, ch, rects5)       # n = 5: the uploaded plan
+        same_records(four, want[:4], f"the inline plan, table {tname}", PLAN_RECTS)
+        same_records(five, want, f"the uploaded plan, table {tname}", rects5)
+        assert four.tobytes() == five[:4].tobytes(), f"records 0 .. 3 of the two plans, table {tname}"
+    ctx.close()
 
 
 def test_sprites_across_a_batch_boundary(R, ref_lib, big):
