@@ -3,6 +3,7 @@
 //   k_blur_copyback default shader, blended            (RC2DGI.cs:381-386)
 //   k_merge         shaders/merge.fs:10-15 + copy-back (RC2DGI.cs:389-404)
 //   k_blur_fused, k_blur_rows: those passes in one kernel where the shapes allow; k_blur_exact: their redo
+//   (k_blur_odd_rows: a row-strip shard's report that its rows need it)
 //   giRT1/2: float4, RGBA16F (f16 mode) or RGBA8 bytes; cascadeBlurRT: float4 (RGBA8 mode: bytes)
 #include "rc2dgi_device.h"
 #include "rc2dgi_kernels.h"
@@ -407,24 +408,58 @@ hipError_t launch_merge(const BlurArgs &a, ScreenDims s, CascadeDims c, hipStrea
   return hipGetLastError();
 }
 
+// A row-strip shard's fused kernels stage rows outside the ones it computed (whole tiles), so they do not report for
+// it (flag nullptr): this scan of the level-0 rows [row0, row1) it did compute does -- every row the redo of its rows
+// reads (plan_frame: level 0 holds the blur's rows +- ceil(radius) + 2).  gi_in as k_blur_rows takes it (g0, gn).
+template <class GI>
+__global__ __launch_bounds__(256) void k_blur_odd_rows(const typename GI::T *__restrict__ gi_in, CascadeDims c,
+                                                       int row0, int row1, int g0, int gn,
+                                                       unsigned *__restrict__ flag, unsigned epoch) {
+  const int i = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int j = row0 + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (i >= c.CW || j >= row1) return;
+  const int gy = min((j - g0) & (c.CH - 1), gn - 1);
+  if (absmax4(GI::ld(&gi_in[(size_t)gy * c.pitch + i])) >= kOddBits) *flag = epoch;
+}
+
+hipError_t launch_blur_odd_rows(const BlurArgs &a, CascadeDims c, hipStream_t st) {
+  if (c.gi_u8 || !(c.powW && c.powH) || !a.flag) return hipErrorInvalidValue;
+  int row0 = a.row0, row1 = a.row1;
+  clamp_rows(c.CH, row0, row1);
+  if (row0 >= row1) return hipSuccess;
+  const int g0 = a.gn <= 0 ? 0 : a.g0, gn = a.gn <= 0 ? c.CH : a.gn;
+  with_gi<false>(c, [&](auto gi) {
+    using GI = decltype(gi);
+    hipLaunchKernelGGL(k_blur_odd_rows<GI>, grid2d(c.CW, row1 - row0), dim3(256), 0, st, tex<GI>(a.gi_in), c, row0,
+                       row1, g0, gn, a.flag, a.epoch);
+  });
+  return hipGetLastError();
+}
+
 // The fused blur kernels' frame redone tap by tap, for a frame in which one of them staged such a value (*flag ==
 // epoch; otherwise every workgroup returns at once).  Each texel evaluates k_blur, k_blur_copyback and (MERGE)
 // k_merge as they are written -- the blur of every texel in its copy-back's LINEAR footprint, the copied-back GI of
 // every texel in the merge's footprint -- from G_0 alone, so no pass waits for another.  Slow (nothing is shared
-// between texels or footprints: 5 blur texels of 9 taps each, 21 with MERGE) and rare.  Whole frames only: no shard
-// windows, no banded G_0.  A workgroup strides over the rows (a small grid: the launch costs little when it is idle).
+// between texels or footprints: 5 blur texels of 9 taps each, 21 with MERGE) and rare.  A workgroup strides over the
+// rows (a small grid: the launch costs little when it is idle).  Rows [row0, row1) of a power-of-two cascade; a
+// row-strip shard's layouts as k_blur_rows has them: gi_in holds rows [g0, g0 + gn) cyclically, temp / color_out
+// hold rows from m0 on, and so do blur_out / gi_out when STRIP (then the rows are the shard's own).
 template <bool MERGE, class GI>
 __global__ __launch_bounds__(256) void k_blur_exact(const unsigned *__restrict__ flag, unsigned epoch,
                                                     const typename GI::T *__restrict__ gi_in,
                                                     float4 *__restrict__ blur_out, typename GI::T *__restrict__ gi_out,
                                                     CascadeDims c, float radius, const float4 *__restrict__ color_in,
                                                     float4 *__restrict__ temp, float4 *__restrict__ color_out,
-                                                    ScreenDims s) {
+                                                    ScreenDims s, int row0, int row1, int m0, int strip, int g0,
+                                                    int gn) {
   if (*flag != epoch) return;
   const int i = blockIdx.x * 64 + (threadIdx.x & 63);
   if (i >= c.CW) return;
   const Axis ax{c.CW, c.powW}, ay{c.CH, c.powH};
   const float tsx = 1.0f / (float)c.CW, tsy = 1.0f / (float)c.CH;
+  auto g0_at = [&](int x, int y) {  // G_0's texel (x, y), 0 <= y < CH
+    return &gi_in[(size_t)min((y - g0) & (c.CH - 1), gn - 1) * c.pitch + x];
+  };
   auto blur_at = [&](int x, int y) {  // k_blur's texel (x, y)
     const float u = texcoord(x, ax), v = texcoord(y, ay);
     const float kx[9] = {-1.f, 1.f, -1.f, 1.f, 0.f, 0.f, -1.f, 1.f, 0.f};
@@ -438,7 +473,12 @@ __global__ __launch_bounds__(256) void k_blur_exact(const unsigned *__restrict__
         sv = v + (ky[k] * tsy) * radius;
         w = k < 4 ? 0.0625f : 0.125f;
       }
-      const float4 t = sample_bilinear_gi<GI>(gi_in, c.pitch, ax, ay, su, sv);
+      int xa, xb, ya, yb;  // (sample_bilinear_gi on the rows as gi_in holds them)
+      float wx, wy;
+      wrap_linear(su, ax, xa, xb, wx);
+      wrap_linear(sv, ay, ya, yb, wy);
+      const float4 t = GI::bilerp(GI::ld_stage(g0_at(xa, ya)), GI::ld_stage(g0_at(xb, ya)),
+                                  GI::ld_stage(g0_at(xa, yb)), GI::ld_stage(g0_at(xb, yb)), wx, wy);
       res.x = res.x + t.x * w;
       res.y = res.y + t.y * w;
       res.z = res.z + t.z * w;
@@ -452,10 +492,10 @@ __global__ __launch_bounds__(256) void k_blur_exact(const unsigned *__restrict__
     wrap_linear(texcoord(x, ax), ax, xa, xb, wx);
     wrap_linear(texcoord(y, ay), ay, ya, yb, wy);
     const float4 sm = GI::RT::bilerp(blur_at(xa, ya), blur_at(xb, ya), blur_at(xa, yb), blur_at(xb, yb), wx, wy);
-    return GI::round(GI::blend(sm, GI::ld(&gi_in[(size_t)y * c.pitch + x])));
+    return GI::round(GI::blend(sm, GI::ld(g0_at(x, y))));
   };
-  for (int j = blockIdx.y * 4 + (threadIdx.x >> 6); j < c.CH; j += 4 * (int)gridDim.y) {
-    const size_t o = (size_t)j * c.pitch + i;
+  for (int j = row0 + blockIdx.y * 4 + (threadIdx.x >> 6); j < row1; j += 4 * (int)gridDim.y) {
+    const size_t o = (size_t)(strip ? j - m0 : j) * c.pitch + i;
     blur_out[o] = blur_at(i, j);
     GI::st(&gi_out[o], gi_at(i, j));
     if constexpr (MERGE) {  // k_merge (cascade == screen)
@@ -464,25 +504,33 @@ __global__ __launch_bounds__(256) void k_blur_exact(const unsigned *__restrict__
       wrap_linear(texcoord(i, Axis{s.W, s.powW}), ax, xa, xb, wx);
       wrap_linear(texcoord(j, Axis{s.H, s.powH}), ay, ya, yb, wy);
       const float4 g = GI::bilerp(gi_at(xa, ya), gi_at(xb, ya), gi_at(xa, yb), gi_at(xb, yb), wx, wy);
-      const size_t so = (size_t)j * s.pitch + i;
+      const size_t so = (size_t)j * s.pitch + i, mo = (size_t)(j - m0) * s.pitch + i;
       const float4 col = color_in[so];
       const float4 src = make_float4(fminf(col.x + g.x, 1.0f), fminf(col.y + g.y, 1.0f), fminf(col.z + g.z, 1.0f), col.w);
       const float4 t = GI::RT::blend_black(src);
-      temp[so] = t;
-      color_out[so] = GI::RT::blend(t, col);
+      temp[mo] = t;
+      color_out[mo] = GI::RT::blend(t, col);
     }
   }
 }
 
 hipError_t launch_blur_exact(const BlurArgs &a, ScreenDims s, CascadeDims c, hipStream_t st) {
-  if (c.gi_u8 || (a.merge && !(s.W == c.CW && s.H == c.CH))) return hipErrorInvalidValue;
-  const dim3 grid(ceil_div(c.CW, 64), min(ceil_div(c.CH, 4), 32));  // (k_blur_exact strides over the rows)
+  if (c.gi_u8 || !(c.powW && c.powH) || (a.merge && !(s.W == c.CW && s.H == c.CH))) return hipErrorInvalidValue;
+  int row0 = a.row0, row1 = a.row1;
+  clamp_rows(c.CH, row0, row1);
+  if (row0 >= row1) return hipSuccess;
+  // (the merge outputs, and blur_out / gi_out when a.strip, start at row m0 and end at m1)
+  const int m1 = a.m1 < 0 ? s.H : a.m1;
+  if ((a.merge || a.strip) && (row0 < a.m0 || row1 > m1)) return hipErrorInvalidValue;
+  const int g0 = a.gn <= 0 ? 0 : a.g0, gn = a.gn <= 0 ? c.CH : a.gn;
+  const dim3 grid(ceil_div(c.CW, 64), min(ceil_div(row1 - row0, 4), 32));  // (k_blur_exact strides over the rows)
   const unsigned *flag = a.flag;
   with_gi<false>(c, [&](auto gi) {
     using GI = decltype(gi);
 #define RC2DGI_BLUR_EXACT(MV)                                                                                \
   hipLaunchKernelGGL((k_blur_exact<MV, GI>), grid, dim3(256), 0, st, flag, a.epoch, tex<GI>(a.gi_in), a.blur_out, \
-                     tex<GI>(a.gi_out), c, a.radius, a.color_in, a.temp, a.color_out, s)
+                     tex<GI>(a.gi_out), c, a.radius, a.color_in, a.temp, a.color_out, s, row0, row1, a.m0,        \
+                     (int)a.strip, g0, gn)
     if (a.merge) RC2DGI_BLUR_EXACT(true); else RC2DGI_BLUR_EXACT(false);
 #undef RC2DGI_BLUR_EXACT
   });

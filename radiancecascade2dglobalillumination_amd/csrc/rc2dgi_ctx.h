@@ -85,8 +85,9 @@ struct rc2dgi_ctx : rc2dgi::Tuning {
   int4 *dboxes = nullptr;            // k_dir_clear's per-bin step boxes (dir_clear_boxes)
   float4 *gi1 = nullptr, *gi2 = nullptr, *blur = nullptr;
   float4 *gi_spare = nullptr;  // fused blur writes the copied-back final GI here, then swaps
-  unsigned *odd_flag = nullptr;  // holds odd_epoch when a fused blur kernel of that frame met a value its skipped
-                                 // weight-0 taps are no identity for (launch_blur_exact then redoes the frame)
+  unsigned *odd_flag = nullptr;  // holds odd_epoch when a fused blur kernel of that frame (a shard: the scan of its
+                                 // level-0 rows) met a value the skipped weight-0 taps are no identity for
+                                 // (launch_blur_exact then redoes the frame, a shard its rows)
   unsigned odd_epoch = 0;
   float2 *dirs = nullptr;  // concatenated per level
   float4 *dexit = nullptr;  // screen-exit terms of dirs (rc_exit_terms), same layout

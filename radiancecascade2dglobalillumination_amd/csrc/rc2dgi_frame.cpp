@@ -356,28 +356,28 @@ static int blur_and_merge(rc2dgi_ctx *c, const FramePlan &plan, float4 *&finalGI
     const bool mrg = c->sd.W == c->CW && c->sd.H == c->CH && !c->linux_merge;
     // The fused kernels skip LINEAR taps of weight 0, an identity but for non-finite or huge neighbours
     // (absmax4, rc2dgi_blur.hip): they report such a value through odd_flag, and the frame is then redone tap by tap
-    // on the device (launch_blur_exact below; one launch that returns at once otherwise).  Whole frames only: a
-    // row-strip shard stages its own rows, so it neither sees every value nor holds every row the redo reads.
-    unsigned *flag = nullptr;
-    if (c->world == 1 && !c->gwin && !c->gband) {
-      if (!c->odd_flag) {
-        HIPCHK(c, alloc(&c->odd_flag, sizeof(unsigned)));
-        HIPCHK(c, hipMemsetAsync(c->odd_flag, 0, sizeof(unsigned), st));
-        c->odd_epoch = 0;
-      }
-      if (++c->odd_epoch == 0) c->odd_epoch = 1;  // (0: the cleared flag)
-      flag = c->odd_flag;
+    // on the device (launch_blur_exact below; one launch that returns at once otherwise).  A row-strip shard's fused
+    // kernels stage whole tiles, rows it did not compute among them, so there a scan of its level-0 rows reports
+    // (launch_blur_odd_rows) and its own rows are redone: the level-0 plan holds every row their redo reads, and a
+    // shard whose rows hold no such value keeps the fused kernels' bits, which are the redo's there.
+    const bool whole = c->world == 1 && !c->gwin && !c->gband;
+    if (!c->odd_flag) {
+      HIPCHK(c, alloc(&c->odd_flag, sizeof(unsigned)));
+      HIPCHK(c, hipMemsetAsync(c->odd_flag, 0, sizeof(unsigned), st));
+      c->odd_epoch = 0;
     }
-    b.flag = flag;
+    if (++c->odd_epoch == 0) c->odd_epoch = 1;  // (0: the cleared flag)
+    unsigned *const flag = c->odd_flag;
+    b.flag = whole ? flag : nullptr;
     b.epoch = c->odd_epoch;
+    b.g0 = c->gband ? c->gb0[0] : 0;
+    b.gn = c->gband ? c->gbn[0] : 0;
     // a fused kernel writes the copied-back GI into gi_spare, which then becomes finalGI: only when
     // every launch of it ran (a refused launch -- shapes it does not take -- falls back before any
     // launch ran, since the shapes are the same for every row interval)
     if (c->blur_path == 0 && blur_rows_plan(c->cd, c->blur_radius, &bt) >= 0) {
       bool ok = true;
       b.merge = mrg;
-      b.g0 = c->gband ? c->gb0[0] : 0;
-      b.gn = c->gband ? c->gbn[0] : 0;
       for (auto &r : plan.blur.iv) ok = ok && launch_blur_rows(rows(r), c->sd, c->cd, st);
       if (!ok && plan.blur.iv.size() > 1) return fail(c, RC2DGI_E_HIP, "fixed-tap blur refused a row interval");
       fused = ok;
@@ -395,7 +395,17 @@ static int blur_and_merge(rc2dgi_ctx *c, const FramePlan &plan, float4 *&finalGI
     if (fused) {
       HIPCHK(c, hipGetLastError());
       b.merge = merged;
-      if (flag) HIPCHK(c, launch_blur_exact(b, c->sd, c->cd, st));
+      b.flag = flag;
+      if (whole) {
+        HIPCHK(c, launch_blur_exact(rows({0, -1}), c->sd, c->cd, st));
+      } else {
+        for (auto &r : plan.level[0].iv) HIPCHK(c, launch_blur_odd_rows(rows(r), c->cd, st));
+        b.strip = c->gwin;
+        if (merged)  // (the merge's outputs hold the own rows)
+          HIPCHK(c, launch_blur_exact(rows({c->ow0, c->ow1}), c->sd, c->cd, st));
+        else
+          for (auto &r : plan.blur.iv) HIPCHK(c, launch_blur_exact(rows(r), c->sd, c->cd, st));
+      }
       if (!c->gwin) std::swap(finalGI, c->gi_spare);  // (gwin: the final GI stays in the strip-sized gi_spare)
     } else {
       for (auto &r : plan.blur.iv) HIPCHK(c, launch_blur(rows(r), c->cd, st));

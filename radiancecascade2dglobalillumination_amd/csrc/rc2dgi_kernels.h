@@ -332,6 +332,8 @@ struct BlurArgs {
   int m0 = 0, m1 = -1;
   int g0 = 0, gn = 0;  // launch_blur_rows: gi_in holds the gn cascade rows from g0 on, cyclically -- a shard's banded
                        // level 0; gn <= 0: every row
+  bool strip = false;  // launch_blur_exact: blur_out / gi_out hold rows [m0, m1) from their row 0 too (a shard's
+                       // strip-sized textures)
 };
 // Blur.fs into blur_out, then the default-shader blended copy-back into gi (RC2DGI.cs:367-387)
 hipError_t launch_blur(const BlurArgs &a, CascadeDims c, hipStream_t st);
@@ -346,9 +348,12 @@ bool launch_blur_fused(const BlurArgs &a, CascadeDims c, hipStream_t st);
 int blur_rows_plan(CascadeDims c, float radius, BlurTaps *bt);
 bool launch_blur_rows(const BlurArgs &a, ScreenDims s, CascadeDims c, hipStream_t st);
 // what launch_blur + launch_blur_copyback (+ launch_merge when a.merge) leave, from gi_in alone into blur_out / gi_out
-// (/ temp / color_out), on the device's say: the kernel returns at once unless *flag == epoch.  Whole frames of
-// power-of-two cascades.
+// (/ temp / color_out), on the device's say: the kernel returns at once unless *flag == epoch.  Rows [row0, row1) of
+// a power-of-two cascade, in a row-strip shard's layouts too (g0 / gn, m0 / m1, strip).
 hipError_t launch_blur_exact(const BlurArgs &a, ScreenDims s, CascadeDims c, hipStream_t st);
+// sets *flag to epoch when rows [row0, row1) of gi_in (g0 / gn) hold a value the fused kernels' skipped taps are no
+// identity for: a row-strip shard's report, over the level-0 rows it computed
+hipError_t launch_blur_odd_rows(const BlurArgs &a, CascadeDims c, hipStream_t st);
 // merge.fs into temp, then tempRT -> colorRT copy-back (RC2DGI.cs:389-404); linux_merge: raylib's default
 // shader in place of merge.fs (RC2DGI_FLAG_LINUX_MERGE_FALLBACK)
 hipError_t launch_merge(const BlurArgs &a, ScreenDims s, CascadeDims c, hipStream_t st, bool linux_merge = false);

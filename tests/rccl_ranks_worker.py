@@ -29,6 +29,10 @@ CASES = [
     # H = 2 mod 4: a step's offset of H / 4 rows ends in .5, its float taps round to the margin row, and that row is
     # one a shard copies from its own window into a block buffer (at 200 x 120 nothing reads those rows)
     (200, 122, 3, 2.0, 1.0, 2.5, 4, "rand:39", "f32", 1),
+    # thin strips (tests/test_shard_edges_cpu.py): one and two rows, every step a block step, a block request received
+    # from three ranks, a step whose taps share one block; two-row strips of a power-of-two screen
+    (64, 12, 2, 2.0, 1.0, 1.5, 8, "rand:37", "f32", 1),
+    (128, 16, 2, 2.0, 1.0, 1.5, 8, "rand:38", "f32", 1),
     (4096, 4096, 6, 2.0, 1.0, 1.5, 2, "demo", "f32", 1),      # strip tables, the smallest size at which they apply
     (4096, 4096, 6, 2.0, 1.0, 1.5, 4, "demo", "f32", 0),      # strip_tables 0: distRT all-broadcast at that size
     (4096, 4096, 6, 2.0, 1.0, 1.5, 8, "speckled", "f32", 1),  # strip tables; records derived from the inputs
