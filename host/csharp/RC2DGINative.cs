@@ -16,7 +16,7 @@ static unsafe class RC2DGINative
 
     public const int OK = 0;
     public enum RT { Color = 0, Emissive = 1, Jump1 = 2, Jump2 = 3, Dist = 4, GI1 = 5, GI2 = 6, Temp = 7, Blur = 8, FinalGI = 9 }
-    public enum Format { RGBA8 = 0, RGBA32F = 1, RGBA16F = 2 }  // RGBA16F: rc2dgi_read / rc2dgi_read_device only
+    public enum Format { RGBA8 = 0, RGBA32F = 1, RGBA16F = 2 }  // RGBA16F: rc2dgi_read* and rc2dgi_write* only
     public enum Storage { F32 = 0, RGBA8Compat = 1, F16 = 2 }  // RGBA8Compat: the shipped app's RGBA8 textures, byte-exact
 
     [StructLayout(LayoutKind.Sequential)]
@@ -137,6 +137,16 @@ static unsafe class RC2DGINative
     public const int ReadFlip = 1;
     [DllImport(Lib)] public static extern int rc2dgi_read(IntPtr ctx, int which, TexRect* rect, int format, int flags, void* host, int pitchBytes);
     [DllImport(Lib)] public static extern int rc2dgi_read_device(IntPtr ctx, int which, TexRect* rect, int format, int flags, void* dev, int pitchBytes);
+
+    // An image into a rectangle of an input (RT.Color or RT.Emissive; rect null: the whole texture), converted on the
+    // device: RGBA32F, RGBA16F (widened exactly) or RGBA8 pixels in rows of pitchBytes (0: tight) become the texels
+    // rc2dgi_upload would store.  WriteFlip: image row 0 is the rectangle's top row.  WriteBlend: the image is blended
+    // over the texels (SRC_ALPHA, ONE_MINUS_SRC_ALPHA on all four channels, what DrawTextureRec into the render texture
+    // does).  dev: aligned to a pixel, as pitchBytes is; a sprite of an atlas is a pointer and a pitch.
+    public const int WriteFlip = 1;
+    public const int WriteBlend = 2;
+    [DllImport(Lib)] public static extern int rc2dgi_write(IntPtr ctx, int which, TexRect* rect, int format, int flags, void* host, int pitchBytes);
+    [DllImport(Lib)] public static extern int rc2dgi_write_device(IntPtr ctx, int which, TexRect* rect, int format, int flags, void* dev, int pitchBytes);
 
     static IntPtr ctx;
     static Config config;

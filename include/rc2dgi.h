@@ -98,9 +98,9 @@ typedef enum rc2dgi_flag {
 typedef enum rc2dgi_format {
   RC2DGI_FMT_RGBA8 = 0,    /* 4 x uint8, unorm (k/255) */
   RC2DGI_FMT_RGBA32F = 1,  /* 4 x float32 */
-  RC2DGI_FMT_RGBA16F = 2   /* 4 x IEEE binary16; accepted by rc2dgi_read / rc2dgi_read_device only: rc2dgi_upload,
-                              rc2dgi_upload_device, rc2dgi_download and rc2dgi_download_level know the two formats
-                              above and refuse this one with RC2DGI_E_ARG */
+  RC2DGI_FMT_RGBA16F = 2   /* 4 x IEEE binary16; accepted by rc2dgi_read / rc2dgi_read_device and rc2dgi_write /
+                              rc2dgi_write_device only: rc2dgi_upload, rc2dgi_upload_device, rc2dgi_download and
+                              rc2dgi_download_level know the two formats above and refuse this one with RC2DGI_E_ARG */
 } rc2dgi_format;
 
 typedef struct rc2dgi_config {
@@ -481,6 +481,62 @@ int rc2dgi_read(rc2dgi_ctx *ctx, int which, const rc2dgi_rect *rect, int format,
                 int pitch_bytes);
 int rc2dgi_read_device(rc2dgi_ctx *ctx, int which, const rc2dgi_rect *rect, int format, int flags, void *dev,
                        int pitch_bytes);
+
+/* ---- an image into a rectangle of an input texture, converted on the device: rc2dgi_read the other way.  (A sprite
+ * or a light cookie drawn with DrawTextureRec into colorRT / emissiveRT, a half tensor of a PyTorch producer, the
+ * 64 x 64 texels of a 4096^2 scene that changed -- without rc2dgi_upload's copy of the whole texture at 16 bytes a
+ * texel and its conversion on one host thread.)
+ *   which, rect   RC2DGI_RT_COLOR or RC2DGI_RT_EMISSIVE, the two inputs (the ids rc2dgi_upload takes); anything else is
+ *            RC2DGI_E_ARG.  The rectangle is valid exactly as for rc2dgi_read: w >= 1, h >= 1, x >= 0, y >= 0,
+ *            w <= W - x and h <= H - y (compared in this form); texels in GL order (row 0 = the bottom); rect == NULL is
+ *            the whole texture.  There is no wrap and no clipping: an invalid rectangle is RC2DGI_E_ARG and nothing is
+ *            written.
+ *   Pixels   pixel (i, j) of the image, 0 <= i < w, 0 <= j < h, goes to texel (x + i, y + j); with RC2DGI_WRITE_FLIP in
+ *            `flags` to texel (x + i, y + h - 1 - j): image row 0 is then the rectangle's TOP row, the order
+ *            rc2dgi_compose and rc2dgi_read(.., RC2DGI_READ_FLIP) produce.
+ *   Values   the inputs are float4 texels in all three storage modes.  The value a pixel becomes:
+ *            RC2DGI_FMT_RGBA32F: the four floats as they are in F32 and F16 storage (a NaN stays a NaN; its payload is
+ *            not part of the contract); in RC2DGI_STORAGE_RGBA8_COMPAT they are quantized as rc2dgi_upload quantizes a
+ *            float image, q8 and then k * (1/255): rint(clamp(x, 0, 1) * 255) * (1.0f / 255.0f), NaN -> 0.
+ *            RC2DGI_FMT_RGBA8: byte k becomes (float)k / 255.0f, one IEEE division, in F32 and F16 storage, and
+ *            (float)k * (1.0f / 255.0f) in RGBA8_COMPAT storage: what rc2dgi_upload and rc2dgi_upload_device make of it.
+ *            RC2DGI_FMT_RGBA16F: each binary16 is widened exactly to float -- a subnormal becomes its exact value,
+ *            +-inf stays +-inf, a NaN stays a NaN (payload unspecified) -- and the result is treated as RGBA32F.  A
+ *            write of the image rc2dgi_read(.., RC2DGI_FMT_RGBA16F) returned, read back as RGBA16F, is that image.
+ *            So a write of the whole texture leaves the bits rc2dgi_upload of the same image leaves, in every storage
+ *            mode, for RGBA32F and RGBA8.
+ *   Blend    without RC2DGI_WRITE_BLEND the value replaces the texel.  With it the texel becomes blend(value, texel),
+ *            the SRC_ALPHA / ONE_MINUS_SRC_ALPHA blend on all four channels that the render textures apply on every
+ *            draw: in F32 and F16 storage value.c * a + texel.c * (1 - a) with a = value.a, every operation single and
+ *            unfused; in RGBA8_COMPAT storage the 8-bit blend min(255, mul8(s8, a8) + mul8(d8, 255 - a8)) * (1/255)
+ *            with s8 = q8(value.c), a8 = q8(value.a), d8 = q8(texel.c) and mul8(x, y) = (x*y*257 + 32768) >> 16.  These
+ *            are the functions rc2dgi_paint blends with: a constant image holding a primitive's colour, blended over
+ *            an integer rectangle, equals rc2dgi_paint of that DrawRectangle without a clear.  A non-finite value or
+ *            alpha gives whatever those expressions give (in float storage NaN and inf propagate by IEEE rules, 0 * inf
+ *            is NaN; in RGBA8_COMPAT storage q8 has clamped them first: NaN and -inf to 0, +inf to 255).
+ *   Pitch    pitch_bytes == 0 is a tight row: w * 16, w * 8 or w * 4 bytes.  Bytes of a source row past the w pixels
+ *            are not read.  rc2dgi_write_device requires `dev` aligned to a pixel (16 / 8 / 4 bytes for RGBA32F /
+ *            RGBA16F / RGBA8) and pitch_bytes a multiple of that; the host variant has no alignment rule.  The source
+ *            must not overlap the context's own textures.
+ * Calls.  rc2dgi_write_device enqueues the kernel on the context stream and returns; `dev` is a device pointer on the
+ * context's device that the caller keeps alive until rc2dgi_sync().  A frame enqueued before the call computes from
+ * the old texels, a frame enqueued after it from the new ones.  rc2dgi_write is synchronous with respect to `host`, as
+ * rc2dgi_upload is: it synchronises the context stream (a cascade chain timeout returns RC2DGI_E_DEVICE), copies rows
+ * into the 8 MiB staging buffer of rc2dgi_read in blocks of whole rows -- the image crosses the bus in its own format
+ * -- runs the kernel per block and returns when the last block is written.  Both do to the context's state what
+ * rc2dgi_upload_device does: a write to COLOR makes COLOR the input again (the old input with the rectangle changed:
+ * the merged output of the last frame is another buffer).  Writing before the first frame is allowed.  Both are
+ * accepted on a row-strip shard, as rc2dgi_upload is: the inputs are replicated whole on every rank, and the caller
+ * writes the same thing on every rank.
+ * Errors, each leaving the context valid and the texture untouched: RC2DGI_E_ARG, checked in this order, for a null
+ * context or source, a bad `which`, a bad `format`, a flag bit other than the two defined, an invalid rectangle, a pitch
+ * smaller than a row and, for the device variant, a misaligned pointer or pitch.  These calls only add exports:
+ * RC2DGI_ABI_VERSION stays 5. */
+enum { RC2DGI_WRITE_FLIP = 1, RC2DGI_WRITE_BLEND = 2 };
+int rc2dgi_write(rc2dgi_ctx *ctx, int which, const rc2dgi_rect *rect, int format, int flags, const void *host,
+                 int pitch_bytes);
+int rc2dgi_write_device(rc2dgi_ctx *ctx, int which, const rc2dgi_rect *rect, int format, int flags, const void *dev,
+                        int pitch_bytes);
 
 /* cascade resolution (RC2DGI.cs:70-77), JFA step count (RC2DGI.cs:289-292) and which
  * giRT holds the final GI (1 or 2, RC2DGI.cs:365) */

@@ -129,8 +129,8 @@ struct rc2dgi_ctx : rc2dgi::Tuning {
                                         // fixed size (reduce_bytes, rc2dgi_regions.cpp), allocated at the first call
   unsigned char *hist_buf = nullptr;    // rc2dgi_histogram's search tree of the edges, then one batch of work items:
                                         // a fixed size (hist_bytes, rc2dgi_regions.cpp), allocated at the first call
-  unsigned char *read_buf = nullptr;    // rc2dgi_read's staged image rows: kReadChunkBytes (rc2dgi_read.h), allocated
-                                        // at the first call
+  unsigned char *read_buf = nullptr;    // rc2dgi_read's and rc2dgi_write's staged image rows: kReadChunkBytes
+                                        // (rc2dgi_read.h), allocated at the first call of either
   std::vector<float> curve_host[RC2DGI_MAX_CURVES];  // rc2dgi_set_curve: slot s at [s - 1], 255 edges; empty: not set
   float *curves_dev = nullptr;          // the same as search trees (rc2dgi_tone.h), 256 words a slot; stored on the
                                         // context stream, allocated at the first rc2dgi_set_curve, kept to the end

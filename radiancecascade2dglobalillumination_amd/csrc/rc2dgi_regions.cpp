@@ -1,9 +1,11 @@
 // rc2dgi_regions.cpp -- the rectangle calls of the C ABI (include/rc2dgi.h): the region statistics (rc2dgi_reduce,
 // rc2dgi_reduce.hip), the histograms (rc2dgi_histogram, rc2dgi_hist.hip) and a rectangle read as an image
-// (rc2dgi_read, rc2dgi_read.hip), each with its _device variant.  The rectangles are validated and cut into work by
-// rc2dgi_rectplan.cpp; here are the argument checks, the uploads and the launches.
+// (rc2dgi_read, rc2dgi_read.hip) and an image written into a rectangle of an input (rc2dgi_write, rc2dgi_write.hip),
+// each with its _device variant.  The rectangles are validated and cut into work by rc2dgi_rectplan.cpp; here are the
+// argument checks, the uploads and the launches.
 #include "rc2dgi_accessory.h"
 #include "rc2dgi_rectplan.h"
+#include "rc2dgi_write.h"
 
 #include <cstddef>
 
@@ -152,6 +154,44 @@ int read_enqueue(rc2dgi_ctx *c, const TexSource &t, const rc2dgi_rect &r, int fo
   return RC2DGI_OK;
 }
 
+// ---- an image into a rectangle of an input
+
+// The checks the two calls share, in the header's order; r becomes the rectangle (the whole texture for null) and
+// *pitch_bytes the tight row where it is 0.  A device source and its pitch are multiples of a pixel; a host source may
+// be anything.  A row-strip shard is accepted as rc2dgi_upload accepts one: the inputs are whole on every rank.
+int write_args(rc2dgi_ctx *c, int which, const rc2dgi_rect *rect, int format, int flags, const void *src,
+               int *pitch_bytes, bool device, rc2dgi_rect &r) {
+  if (!c) return RC2DGI_E_ARG;
+  RC2DGI_USABLE(c);
+  if (!src) return fail(c, RC2DGI_E_ARG, "write: null argument");
+  if (which != RC2DGI_RT_COLOR && which != RC2DGI_RT_EMISSIVE)
+    return fail(c, RC2DGI_E_ARG, "write: only COLOR and EMISSIVE are inputs");
+  if (format != RC2DGI_FMT_RGBA8 && format != RC2DGI_FMT_RGBA32F && format != RC2DGI_FMT_RGBA16F)
+    return fail(c, RC2DGI_E_ARG, "write: bad format");
+  if (flags & ~(RC2DGI_WRITE_FLIP | RC2DGI_WRITE_BLEND))
+    return fail(c, RC2DGI_E_ARG, "write: the flags are RC2DGI_WRITE_FLIP and RC2DGI_WRITE_BLEND");
+  r = rect ? *rect : rc2dgi_rect{0, 0, c->W, c->H};
+  if (!rect_valid(r, c->W, c->H))
+    return fail(c, RC2DGI_E_ARG, "write: the rectangle does not lie inside the texture (no wrap, no clipping)");
+  const int pxb = read_pixel_bytes(format), row = r.w * pxb;  // (w <= 32768)
+  if (*pitch_bytes == 0) *pitch_bytes = row;
+  if (*pitch_bytes < row) return fail(c, RC2DGI_E_ARG, "write: pitch smaller than a row");
+  if (device && (!aligned_to(src, (uintptr_t)pxb) || *pitch_bytes % pxb != 0))
+    return fail(c, RC2DGI_E_ARG, "write: the source and the pitch are multiples of a pixel (16 / 8 / 4 bytes)");
+  return RC2DGI_OK;
+}
+
+// image rows [j0, j0 + rows) of rectangle r from src (the first of them at src), enqueued on the context stream
+int write_enqueue(rc2dgi_ctx *c, int which, const rc2dgi_rect &r, int format, int flags, int j0, int rows,
+                  const void *src, size_t pitch) {
+  const bool flip = (flags & RC2DGI_WRITE_FLIP) != 0;
+  const WriteArgs a{which == RC2DGI_RT_COLOR ? c->color_in : c->emissive, c->sd.pitch, r.x, r.w,
+                    flip ? r.y + r.h - 1 - j0 : r.y + j0, flip ? -1 : 1, rows,
+                    static_cast<const unsigned char *>(src), pitch};
+  HIPCHK(c, launch_write(a, format, rgba8(c), (flags & RC2DGI_WRITE_BLEND) != 0, c->stream));
+  return RC2DGI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -214,6 +254,38 @@ int rc2dgi_read(rc2dgi_ctx *c, int which, const rc2dgi_rect *rect, int format, i
     if (int rc = read_enqueue(c, t, r, format, flags, j0, rows, c->read_buf, spitch)) return rc;
     HIPCHK(c, hipMemcpy2DAsync(static_cast<unsigned char *>(host) + (size_t)j0 * (size_t)pitch_bytes, (size_t)pitch_bytes,
                                c->read_buf, spitch, row, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RC2DGI_OK;
+}
+
+int rc2dgi_write_device(rc2dgi_ctx *c, int which, const rc2dgi_rect *rect, int format, int flags, const void *dev,
+                        int pitch_bytes) {
+  rc2dgi_rect r{};
+  if (int rc = write_args(c, which, rect, format, flags, dev, &pitch_bytes, true, r)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = write_enqueue(c, which, r, format, flags, 0, r.h, dev, (size_t)pitch_bytes)) return rc;
+  if (which == RC2DGI_RT_COLOR) c->frame_done = false;
+  return RC2DGI_OK;
+}
+
+int rc2dgi_write(rc2dgi_ctx *c, int which, const rc2dgi_rect *rect, int format, int flags, const void *host,
+                 int pitch_bytes) {
+  rc2dgi_rect r{};
+  if (int rc = write_args(c, which, rect, format, flags, host, &pitch_bytes, false, r)) return rc;
+  if (int rc = host_begin(c)) return rc;
+  // rc2dgi_read's staging the other way: a block's rows go up in the image's own format, padded to whole 16-byte
+  // lines, and its kernel follows on the stream; the copy of the next block waits for that kernel.  The copy has
+  // consumed the (pageable) host rows when it returns.
+  const size_t row = (size_t)r.w * read_pixel_bytes(format), spitch = read_staged_pitch(row);
+  const int block = read_block_rows(row, r.h);
+  if (!c->read_buf) HIPCHK(c, alloc(&c->read_buf, kReadChunkBytes));
+  for (int j0 = 0; j0 < r.h; j0 += block) {
+    const int rows = std::min(block, r.h - j0);
+    HIPCHK(c, hipMemcpy2DAsync(c->read_buf, spitch, static_cast<const unsigned char *>(host) + (size_t)j0 * (size_t)pitch_bytes,
+                               (size_t)pitch_bytes, row, (size_t)rows, hipMemcpyHostToDevice, c->stream));
+    if (int rc = write_enqueue(c, which, r, format, flags, j0, rows, c->read_buf, spitch)) return rc;
+    if (which == RC2DGI_RT_COLOR) c->frame_done = false;  // (a later block may fail: the texture has changed)
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RC2DGI_OK;

@@ -33,6 +33,8 @@ SCREEN_RTS = ("color", "emissive", "jump1", "jump2", "dist", "temp")
 FMT_RGBA8, FMT_RGBA32F = 0, 1
 FMT_RGBA16F = 2  # IEEE binary16, round to nearest even: read / read_into only (upload and download refuse it)
 READ_FLIP = 1    # rc2dgi_read: image row 0 is the rectangle's top row
+WRITE_FLIP = 1   # rc2dgi_write: image row 0 is the rectangle's top row
+WRITE_BLEND = 2  # rc2dgi_write: the image is blended over the texels (SRC_ALPHA, ONE_MINUS_SRC_ALPHA)
 _READ_FORMATS = {"float32": FMT_RGBA32F, "float16": FMT_RGBA16F, "uint8": FMT_RGBA8}  # by numpy / torch dtype name
 STATUS = {0: "OK", -1: "E_ARG", -2: "E_UNIFORM", -3: "E_HIP", -4: "E_OOM", -5: "E_UNSUPPORTED", -6: "E_STATE", -7: "E_DEVICE"}
 PASS_NAMES = ("screenuv", "jfa", "rc", "blur", "merge", "total")
@@ -276,6 +278,8 @@ def load_library(path: Optional[str] = None):
                                     ctypes.c_int),
         "rc2dgi_read": ([vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int], ctypes.c_int),
         "rc2dgi_read_device": ([vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int], ctypes.c_int),
+        "rc2dgi_write": ([vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int], ctypes.c_int),
+        "rc2dgi_write_device": ([vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -705,6 +709,43 @@ class RC2DGI:
         self._check(self._L.rc2dgi_read_device(self._h, w, None if r is None else r.ctypes.data_as(ctypes.c_void_p), fmt,
                                                READ_FLIP if flip else 0, ctypes.c_void_p(dst.data_ptr()), pitch),
                     "read_into")
+
+    # ---------------------------------------------------------------- an image into a rectangle of an input
+    def write(self, which, img, rect=None, flip=False, blend=False) -> None:
+        """An (h, w, 4) image into a rectangle of an input texture, converted on the GPU (rc2dgi_write /
+        rc2dgi_write_device): which -- "color" or "emissive" (or the rc2dgi_rt id); rect -- (x, y, w, h) in texels, GL
+        order (row 0 = the bottom), None: the whole texture; flip -- image row 0 is the rectangle's top row; blend --
+        the image is blended over the texels (SRC_ALPHA, ONE_MINUS_SRC_ALPHA on all four channels) instead of replacing
+        them.  The dtype float32 / float16 / uint8 selects the format; the texels become what upload would store.
+        img: a numpy array (synchronous; its row stride is the pitch, any whole number of bytes) or a torch tensor on
+        this context's GPU with contiguous pixels (enqueued on the context stream; its row stride is the pitch, so a
+        view of a larger tensor is accepted as read_into accepts one; keep it alive until sync())."""
+        w, r, (rw, rh) = self._read_rect(which, rect)
+        flags = (WRITE_FLIP if flip else 0) | (WRITE_BLEND if blend else 0)
+        rp = None if r is None else r.ctypes.data_as(ctypes.c_void_p)
+        if hasattr(img, "data_ptr"):
+            if not getattr(img, "is_cuda", False) or img.device.index != self.device:
+                raise TypeError("write: expected a numpy array or a tensor on this context's GPU")
+            fmt = _READ_FORMATS.get(str(img.dtype).replace("torch.", ""))
+            if fmt is None:
+                raise TypeError("write: expected a float32, float16 or uint8 tensor")
+            if img.dim() != 3 or tuple(img.shape) != (rh, rw, 4) or img.stride(2) != 1 or img.stride(1) != 4:
+                raise ValueError(f"write: expected shape ({rh}, {rw}, 4) with contiguous pixels, got {tuple(img.shape)}")
+            pitch = int(img.stride(0)) * img.element_size() if rh > 1 else 0
+            self._check(self._L.rc2dgi_write_device(self._h, w, rp, fmt, flags, ctypes.c_void_p(img.data_ptr()), pitch),
+                        "write (device)")
+            return
+        a = np.asarray(img)
+        fmt = _READ_FORMATS.get(a.dtype.name)
+        if fmt is None:
+            raise TypeError("write: dtype is float32, float16 or uint8")
+        if a.shape != (rh, rw, 4):
+            raise ValueError(f"write: expected shape ({rh}, {rw}, 4), got {a.shape}")
+        px = 4 * a.itemsize
+        if a.strides[2] != a.itemsize or a.strides[1] != px or (rh > 1 and a.strides[0] < rw * px):
+            a = np.ascontiguousarray(a)  # (pixels apart, or rows that overlap or run backwards: a tight copy)
+        pitch = int(a.strides[0]) if rh > 1 else 0
+        self._check(self._L.rc2dgi_write(self._h, w, rp, fmt, flags, ctypes.c_void_p(a.ctypes.data), pitch), "write")
 
     def set_tuning(self, key: str, value: int) -> None:
         """Performance knobs (results are identical for every value), e.g. rc_variant."""
