@@ -545,7 +545,10 @@ const char *rc2dgi_last_error(rc2dgi_ctx *ctx);
 int rc2dgi_abi_version(void);
 
 /* ---- stream / timing.  rc2dgi_set_stream: run on a caller-owned hipStream_t on the
- * context's device (NULL = back to the context's own stream).  rc2dgi_set_timing(ctx, mode):
+ * context's device (NULL = back to the context's own stream).  It waits until the stream the
+ * context leaves has run everything enqueued on it, so what follows on the new stream sees the
+ * frames and writes enqueued before the call, whatever the two streams know of each other; the
+ * caller orders the new stream's own earlier work.  rc2dgi_set_timing(ctx, mode):
  * 0 off; 1 rc2dgi_do() records HIP events around each pass and each RC level; 2 around each
  * pass only (every event idles the GPU a few microseconds before the next kernel, so mode 2
  * times the RC pass as it runs untimed).  rc2dgi_pass_times() returns the last frame's
