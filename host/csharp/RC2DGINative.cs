@@ -49,6 +49,13 @@ static unsafe class RC2DGINative
         public byte R, G, B, A;
     }
     [DllImport(Lib)] public static extern int rc2dgi_paint(IntPtr ctx, int which, byte* clearRgba, Prim* prims, int n);
+    // The same painting from n Prim records in device memory (primsDev, aligned to 4 bytes; n up to 1 << 20), enqueued on
+    // the context stream: nothing waits.  countDev: null, or one int on the device read when the work runs -- min(max(count,
+    // 0), n) primitives are painted.  statusDev: null, or two ints that receive {painted, refused}: a primitive rc2dgi_paint
+    // would refuse draws nothing and is counted.  rc2dgi_paint_device_limits (host-only): the primitives of one batch and
+    // the bytes of working memory the context allocates at the first call, for a config.
+    [DllImport(Lib)] public static extern int rc2dgi_paint_device(IntPtr ctx, int which, byte* clearRgba, void* primsDev, int n, void* countDev, void* statusDev);
+    [DllImport(Lib)] public static extern int rc2dgi_paint_device_limits(ref Config cfg, out int batchPrims, out long workBytes);
 
     // rc2dgi_view: one draw of the display frame (window rectangle, y down; Filter 0 = the texture's own,
     // 1 POINT, 2 LINEAR; border A == 0: none)

@@ -675,6 +675,48 @@ typedef struct rc2dgi_prim {
 enum { RC2DGI_PRIM_RECT = 0, RC2DGI_PRIM_CIRCLE = 1 };
 int rc2dgi_paint(rc2dgi_ctx *ctx, int which, const unsigned char *clear_rgba, const rc2dgi_prim *prims, int n);
 
+/* ---- the same painting from a primitive list in device memory, enqueued on the context stream.  (Discs and squares
+ * a PyTorch producer keeps in a tensor -- a particle system used as lights -- painted without a trip to the host, in a
+ * loop that never waits: paint, rc2dgi_do, rc2dgi_read_device.)
+ *   prims_dev  n records of rc2dgi_prim (24 bytes each) on the context's device, aligned to 4 bytes; 0 <= n <= 1 << 20.
+ *              n == 0 admits a null prims_dev.
+ *   count_dev  NULL, or one int32 on the device, aligned to 4 bytes, read on the stream when the work runs: the number
+ *              painted is m = min(max(*count_dev, 0), n).  With NULL, m = n.  m == 0 with a clear colour is a clear
+ *              only; m == 0 without one leaves the texture as it is.
+ *   status_dev NULL, or two int32 on the device, aligned to 4 bytes: the call writes {m, refused} there on the stream,
+ *              both words on every call, m == 0 included.
+ *   Result     `which`, clear_rgba, draw order, coverage rule, colour conversion, blend and the three storage modes are
+ *              those of rc2dgi_paint: for a list rc2dgi_paint accepts, the texture afterwards holds the bits that
+ *              rc2dgi_paint(ctx, which, clear_rgba, list, m) leaves.
+ *   Refused    the device cannot fail a call, so a primitive that rc2dgi_paint would answer with RC2DGI_E_ARG draws
+ *              nothing and is counted in `refused`; the other primitives are unaffected.  With lim = 2^22 and the test
+ *              ok(c) = fabsf(c) < lim (false for a NaN and for an infinity), a primitive is refused when
+ *                kind is neither RC2DGI_PRIM_RECT nor RC2DGI_PRIM_CIRCLE, or
+ *                !ok(x), !ok(y) or !ok(w); for a rectangle also !ok(h), !ok(x + w) or !ok(y + h), the sums in float;
+ *                for a circle also !(fabsf(x) + fabsf(w) < lim) or !(fabsf(y) + fabsf(w) < lim) (its h is not read).
+ *              Nothing read from prims_dev or count_dev becomes an address, an index or a loop bound before it has
+ *              passed this test or that clamp and the primitive's pixel box has been clipped to the target: a buffer
+ *              of garbage paints nothing and faults nothing.
+ *   Order      the call is enqueued behind whatever is in flight on the context stream and returns; it does not wait
+ *              for the stream or the device (the first call of a context allocates the working memory, the one
+ *              exception).  The caller keeps the three buffers alive until rc2dgi_sync() and may overwrite them on the
+ *              same stream as soon as the call has returned.  A frame enqueued before the call sees the old texels, a
+ *              frame enqueued after it the new ones.  Painting COLOR makes COLOR the input again, as rc2dgi_paint does.
+ *              Row-strip shards accept the call as they accept rc2dgi_paint.
+ *   Memory     the context owns the working memory: allocated at the first call, freed with the context, its size
+ *              fixed by the screen size whatever n is, at most 64 MiB.  A list longer than one batch is painted batch
+ *              after batch on the stream, the draw order kept across batches (three kernels a batch of the n given,
+ *              whatever *count_dev turns out to be: an empty batch's kernels leave at once).
+ *              rc2dgi_paint_device_limits (host-only, no device) reports for a config the batch capacity (2048, 4096
+ *              or 8192 primitives, by screen size) and the working bytes; either pointer may be NULL.
+ * Errors, each leaving the context valid and the texture untouched: RC2DGI_E_ARG, checked in this order, for a null
+ * context, a bad `which`, n out of range, a null prims_dev with n > 0, a misaligned pointer;
+ * rc2dgi_paint_device_limits: RC2DGI_E_ARG for a null config or a screen size rc2dgi_create refuses.  These calls only
+ * add exports: RC2DGI_ABI_VERSION stays 5. */
+int rc2dgi_paint_device(rc2dgi_ctx *ctx, int which, const unsigned char *clear_rgba, const void *prims_dev, int n,
+                        const void *count_dev, void *status_dev);
+int rc2dgi_paint_device_limits(const rc2dgi_config *cfg, int *batch_prims, long long *work_bytes);
+
 /* ---- row-strip sharding of one frame over `world` ranks.
  * rc2dgi_set_shard: the context computes screen rows [rank*H/world, (rank+1)*H/world) of the
  * merged colorRT / tempRT and exactly what they depend on (world = 1: the whole frame again).

@@ -78,6 +78,7 @@ void free_buffers(rc2dgi_ctx *c) {
   free_chain(c);
   c->rc_maps.clear();
   c->paint_buf.release();
+  c->paint_dev.release();
   if (c->present_buf) (void)hipFree(c->present_buf);
   c->present_buf = nullptr;
   c->present_cap = 0;

@@ -246,6 +246,35 @@ int rc2dgi_paint(rc2dgi_ctx *c, int which, const unsigned char *clear_rgba, cons
   return RC2DGI_OK;
 }
 
+int rc2dgi_paint_device(rc2dgi_ctx *c, int which, const unsigned char *clear_rgba, const void *prims_dev, int n,
+                        const void *count_dev, void *status_dev) {
+  if (!c) return RC2DGI_E_ARG;
+  RC2DGI_USABLE(c);
+  if (which != RC2DGI_RT_COLOR && which != RC2DGI_RT_EMISSIVE)
+    return fail(c, RC2DGI_E_ARG, "only COLOR and EMISSIVE are painted");
+  if (n < 0 || n > (1 << 20)) return fail(c, RC2DGI_E_ARG, "paint_device: n is 0 .. 1 << 20");
+  if (n > 0 && !prims_dev) return fail(c, RC2DGI_E_ARG, "paint_device: null primitive list");
+  for (const void *p : {prims_dev, count_dev, static_cast<const void *>(status_dev)})
+    if (reinterpret_cast<uintptr_t>(p) % 4 != 0)
+      return fail(c, RC2DGI_E_ARG, "paint_device: the list, the count and the status are aligned to 4 bytes");
+  HIPCHK(c, hipSetDevice(c->device));
+  float4 *dst = which == RC2DGI_RT_COLOR ? c->color_in : c->emissive;
+  HIPCHK(c, paint_prims_device(dst, c->W, c->H, c->sd.pitch, rgba8(c), clear_rgba, prims_dev, n, count_dev, status_dev,
+                               c->paint_dev, c->stream));
+  if (which == RC2DGI_RT_COLOR) c->frame_done = false;
+  return RC2DGI_OK;
+}
+
+int rc2dgi_paint_device_limits(const rc2dgi_config *cfg, int *batch_prims, long long *work_bytes) {
+  if (!cfg || cfg->screen_width <= 0 || cfg->screen_height <= 0 || cfg->screen_width > 32768 ||
+      cfg->screen_height > 32768)
+    return RC2DGI_E_ARG;
+  const PaintDevPlan plan = paint_dev_plan(cfg->screen_width, cfg->screen_height);
+  if (batch_prims) *batch_prims = plan.batch;
+  if (work_bytes) *work_bytes = (long long)plan.bytes;
+  return RC2DGI_OK;
+}
+
 int rc2dgi_upload_device(rc2dgi_ctx *c, int which, const void *dev, int pitch_bytes, int format) {
   if (!c || !dev) return fail(c, RC2DGI_E_ARG, "null argument");
   RC2DGI_USABLE(c);

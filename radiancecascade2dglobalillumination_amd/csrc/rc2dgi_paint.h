@@ -26,4 +26,33 @@ struct PaintBuffers {
 hipError_t paint_prims(float4 *dst, int W, int H, int pitch, bool u8, const unsigned char *clear,
                        const rc2dgi_prim *prims, int n, PaintBuffers &buf, hipStream_t st);
 
+// raylib's host-side cosf / sinf of DEG2RAD * 10k, k = 0 .. 36 (glibc's, as paint_prims uses them)
+void paint_circle_table(float cos37[37], float sin37[37]);
+
+// ---- rc2dgi_paint_device (rc2dgi_paint_dev.hip): the same painting from a primitive list in device memory, set up,
+// binned and rasterised on the device.
+// The plan of a W x H target (host arithmetic only): a tile is 64 x tile_h pixels, a batch `batch` primitives, and the
+// working memory holds, in this order, kPaintDevHead bytes of counters, `batch` set-up records, batch * 36 triangle
+// records and one mask of `batch` bits a tile.
+struct PaintDevPlan {
+  int tile_h = 4;     // 4 .. 128, a power of two
+  int batch = 8192;   // 2048, 4096 or 8192: 64 lanes x (batch / 2048) words x 32 bits
+  int tiles_x = 0, tiles_y = 0;
+  size_t off_prims = 0, off_tris = 0, off_masks = 0, bytes = 0;
+};
+PaintDevPlan paint_dev_plan(int W, int H);
+
+struct PaintDevBuffers {
+  unsigned char *work = nullptr;  // PaintDevPlan::bytes, allocated at the first call; the masks and counters are zero
+                                  // between calls (the kernels leave them so)
+  void release();
+  ~PaintDevBuffers() { release(); }
+};
+
+// enqueues the whole painting on `st` and returns (no wait but the first call's allocation).  prims_dev: n records of
+// rc2dgi_prim; count_dev: null or one int32; status_dev: null or two int32 {m, refused}.
+hipError_t paint_prims_device(float4 *dst, int W, int H, int pitch, bool u8, const unsigned char *clear,
+                              const void *prims_dev, int n, const void *count_dev, void *status_dev,
+                              PaintDevBuffers &buf, hipStream_t st);
+
 }  // namespace rc2dgi

@@ -17,6 +17,7 @@
 // bounding box meets the tile into LDS, then each pixel walks that short list.
 #include "rc2dgi_paint.h"
 #include "rc2dgi_device.h"
+#include "rc2dgi_paint_raster.h"
 
 #include <algorithm>
 #include <climits>
@@ -25,24 +26,6 @@
 #include <vector>
 
 namespace rc2dgi {
-
-struct PaintEdge {
-  int a, b;     // E(X, Y) = a*X + b*Y + c over 1/256-pixel window coordinates
-  long long c;
-};
-
-struct PaintTri {
-  PaintEdge e[3];
-  unsigned incl;  // bit k: pixel centres exactly on edge k are covered
-  unsigned pad[3];
-};
-
-struct PaintPrim {
-  int x0, y0, x1, y1;  // pixel bounding box (inclusive, GL rows), already clipped to the target
-  int tri0, ntri;
-  int pad0, pad1;
-  float4 color;        // unorm8 * (1/255)
-};
 
 constexpr int kPaintChunk = 1024;  // primitives compacted per pass of a workgroup
 
@@ -82,18 +65,7 @@ __global__ __launch_bounds__(256) void k_paint(float4 *__restrict__ dst, int W, 
     for (int q = 0; q < cnt; ++q) {
       const PaintPrim &p = prims[list[q]];
       if (!in || i < p.x0 || i > p.x1 || j < p.y0 || j > p.y1) continue;
-      bool cov = false;
-      for (int t = p.tri0; t < p.tri0 + p.ntri && !cov; ++t) {
-        const PaintTri &tr = tris[t];
-        bool ok = true;
-#pragma unroll
-        for (int e = 0; e < 3; ++e) {
-          const long long E = (long long)tr.e[e].a * X + (long long)tr.e[e].b * Y + tr.e[e].c;
-          ok = ok && (E > 0 || (E == 0 && ((tr.incl >> e) & 1u)));
-        }
-        cov = ok;
-      }
-      if (cov)  // SRC_ALPHA, ONE_MINUS_SRC_ALPHA on all four channels (unfused; RGBA8: in 8 bits)
+      if (paint_covered(p, tris, X, Y))  // SRC_ALPHA, ONE_MINUS_SRC_ALPHA on all four channels (unfused; RGBA8: in 8 bits)
         v = u8 ? GiU8::blend(p.color, v) : GiF32::blend(p.color, v);
     }
     __syncthreads();  // flag / list are rewritten by the next chunk
@@ -138,7 +110,18 @@ Snap to_window(V2 v, int W, int H) {
 
 long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
+const CircleTable &circle_table() {
+  static const CircleTable tab;
+  return tab;
+}
+
 }  // namespace
+
+void paint_circle_table(float cos37[37], float sin37[37]) {
+  const CircleTable &tab = circle_table();
+  std::memcpy(cos37, tab.c, sizeof tab.c);
+  std::memcpy(sin37, tab.s, sizeof tab.s);
+}
 
 void PaintBuffers::release() {
   if (prims) (void)hipFree(prims);
@@ -149,7 +132,7 @@ void PaintBuffers::release() {
 
 hipError_t paint_prims(float4 *dst, int W, int H, int pitch, bool u8, const unsigned char *clear, const rc2dgi_prim *in,
                        int n, PaintBuffers &buf, hipStream_t st) {
-  static const CircleTable tab;
+  const CircleTable &tab = circle_table();
   std::vector<PaintPrim> hp;
   std::vector<PaintTri> ht;
   hp.reserve(n);

@@ -280,6 +280,9 @@ def load_library(path: Optional[str] = None):
         "rc2dgi_read_device": ([vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int], ctypes.c_int),
         "rc2dgi_write": ([vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int], ctypes.c_int),
         "rc2dgi_write_device": ([vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int], ctypes.c_int),
+        "rc2dgi_paint_device": ([vp, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), vp, ctypes.c_int, vp, vp],
+                                ctypes.c_int),
+        "rc2dgi_paint_device_limits": ([ctypes.POINTER(_Config), ip, ctypes.POINTER(ctypes.c_longlong)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -452,6 +455,35 @@ class RC2DGI:
                           *(int(v) for v in p[5:9]))
         cl = None if clear is None else (ctypes.c_ubyte * 4)(*[int(v) for v in clear])
         self._check(self._L.rc2dgi_paint(self._h, RT[which], cl, arr, len(prims)), f"paint {which}")
+
+    def paint_device(self, which, prims, clear=None, count=None, status=None) -> None:
+        """The same painting from a primitive list in device memory, enqueued on the context stream
+        (rc2dgi_paint_device): nothing waits.  prims: a contiguous torch.int32 (n, 6) tensor on this context's GPU, a row
+        the six words of rc2dgi_prim (pack_prims makes one); count: None or an int32 tensor of one element, read on
+        the stream when the work runs -- min(max(count, 0), n) primitives are painted; status: None or an int32 tensor
+        of two elements that receives {painted, refused}.  A primitive paint() would raise on draws nothing and is
+        counted in `refused`.  Keep the tensors alive until sync(); they may be overwritten on the same stream as soon
+        as the call has returned."""
+        w = RT[which] if isinstance(which, str) else int(which)
+
+        def dev_i32(t, what, numel=None):
+            if not getattr(t, "is_cuda", False) or t.device.index != self.device:
+                raise TypeError(f"paint_device: {what}: expected a tensor on this context's GPU")
+            if str(t.dtype) != "torch.int32" or not t.is_contiguous():
+                raise TypeError(f"paint_device: {what}: expected a contiguous int32 tensor")
+            if numel is not None and t.numel() != numel:
+                raise ValueError(f"paint_device: {what}: expected {numel} element(s), got {t.numel()}")
+            return ctypes.c_void_p(t.data_ptr())
+
+        p = dev_i32(prims, "prims")
+        if prims.dim() != 2 or prims.shape[1] != 6:
+            raise ValueError(f"paint_device: expected (n, 6) words, got {tuple(prims.shape)}")
+        n = int(prims.shape[0])
+        cl = None if clear is None else (ctypes.c_ubyte * 4)(*[int(v) for v in clear])
+        self._check(self._L.rc2dgi_paint_device(self._h, w, cl, p if n else None, n,
+                                                None if count is None else dev_i32(count, "count", 1),
+                                                None if status is None else dev_i32(status, "status", 2)),
+                    f"paint_device {which}")
 
     def download(self, which: str, dtype=np.float32) -> np.ndarray:
         w = RT[which]
@@ -899,6 +931,34 @@ def display_layout(W: int, H: int, max_views: int = 8):
     if n < 0:
         raise RC2DGIError(n, "rc2dgi_display_layout")
     return [View.from_buffer_copy(arr[k]) for k in range(min(n, max_views))]
+
+
+def pack_prims(kind, xywh, rgba):
+    """The (n, 6) int32 tensor RC2DGI.paint_device takes, from device tensors with torch ops alone (nothing leaves the
+    device, nothing waits): kind (n,) of any integer dtype (0 rectangle, 1 circle), xywh (n, 4) float32 (circle: x, y
+    the centre, w the radius), rgba (n, 4) uint8.  The float bits are reinterpreted; the four colour bytes go little-
+    endian into word 5, as rc2dgi_prim lays them out."""
+    import torch
+
+    n = int(kind.shape[0])
+    if tuple(xywh.shape) != (n, 4) or xywh.dtype != torch.float32:
+        raise ValueError(f"pack_prims: xywh is ({n}, 4) float32, got {tuple(xywh.shape)} {xywh.dtype}")
+    if tuple(rgba.shape) != (n, 4) or rgba.dtype != torch.uint8:
+        raise ValueError(f"pack_prims: rgba is ({n}, 4) uint8, got {tuple(rgba.shape)} {rgba.dtype}")
+    return torch.cat([kind.reshape(n, 1).to(torch.int32), xywh.contiguous().view(torch.int32),
+                      rgba.contiguous().view(torch.int32)], dim=1)
+
+
+def paint_device_limits(W: int, H: int):
+    """Host-only: (batch_prims, work_bytes) of RC2DGI.paint_device on a W x H screen (rc2dgi_paint_device_limits): how
+    many primitives one batch holds and the working memory the context allocates at the first call."""
+    L = load_library()
+    cfg = _Config(screen_width=W, screen_height=H)  # (the only fields rc2dgi_paint_device_limits reads)
+    batch, work = ctypes.c_int(), ctypes.c_longlong()
+    rc = L.rc2dgi_paint_device_limits(ctypes.byref(cfg), ctypes.byref(batch), ctypes.byref(work))
+    if rc != 0:
+        raise RC2DGIError(rc, f"rc2dgi_paint_device_limits({W}x{H})")
+    return batch.value, work.value
 
 
 def check_edges(edges) -> bool:
