@@ -1,7 +1,7 @@
 /* layout.c -- sizeof / offsetof of the ABI structs, as the C compiler lays them out, for
  * tests/test_host_cpu.py to compare with the C# StructLayout(Sequential) mirrors in
  * host/csharp/RC2DGINative.cs (Config, Prim; View: tests/test_present_cpu.py; Ray, RayHit: tests/test_query_cpu.py;
- * Rect, Stats: tests/test_reduce_cpu.py; Tone: tests/test_tone_cpu.py). */
+ * Rect, Stats: tests/test_reduce_cpu.py; Tone: tests/test_tone_cpu.py; Atlas, Sprite: tests/test_sprites_cpu.py). */
 #include <stddef.h>
 #include <stdio.h>
 
@@ -75,5 +75,23 @@ int main(void) {
   printf("rc2dgi_tone %zu\n", sizeof(rc2dgi_tone));
   F(rc2dgi_tone, exposure);
   F(rc2dgi_tone, curve);
+  printf("rc2dgi_atlas %zu\n", sizeof(rc2dgi_atlas));
+  F(rc2dgi_atlas, dev);
+  F(rc2dgi_atlas, w);
+  F(rc2dgi_atlas, h);
+  F(rc2dgi_atlas, pitch_bytes);
+  F(rc2dgi_atlas, format);
+  printf("rc2dgi_sprite %zu\n", sizeof(rc2dgi_sprite));
+  F(rc2dgi_sprite, sx);
+  F(rc2dgi_sprite, sy);
+  F(rc2dgi_sprite, w);
+  F(rc2dgi_sprite, h);
+  F(rc2dgi_sprite, dx);
+  F(rc2dgi_sprite, dy);
+  F(rc2dgi_sprite, r);
+  F(rc2dgi_sprite, g);
+  F(rc2dgi_sprite, b);
+  F(rc2dgi_sprite, a);
+  F(rc2dgi_sprite, flags);
   return 0;
 }

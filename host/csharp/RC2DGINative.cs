@@ -57,6 +57,30 @@ static unsafe class RC2DGINative
     [DllImport(Lib)] public static extern int rc2dgi_paint_device(IntPtr ctx, int which, byte* clearRgba, void* primsDev, int n, void* countDev, void* statusDev);
     [DllImport(Lib)] public static extern int rc2dgi_paint_device_limits(ref Config cfg, out int batchPrims, out long workBytes);
 
+    // rc2dgi_sprites_device: n Sprite records in device memory, each the rectangle (Sx, Sy, W, H) of one atlas image
+    // (a device image whose row 0 is the top row) drawn 1:1 with its top-left pixel at (Dx, Dy), raylib screen
+    // coordinates -- DrawTextureRec at an integer position -- tinted and blended over the texels (SpriteReplace:
+    // replacing them) with rc2dgi_write's values.  List, count and status as for rc2dgi_paint_device; the working memory
+    // is the one rc2dgi_paint_device_limits reports.  Keep the atlas alive until rc2dgi_sync.
+    [StructLayout(LayoutKind.Sequential)]
+    public struct Atlas
+    {
+        public void* Dev;
+        public int W, H;
+        public int PitchBytes;         // 0 = tight
+        public int Format;             // 0 RGBA8, 1 RGBA32F, 2 RGBA16F
+    }
+    [StructLayout(LayoutKind.Sequential, Size = 32)]
+    public struct Sprite
+    {
+        public int Sx, Sy, W, H;
+        public int Dx, Dy;
+        public byte R, G, B, A;        // tint
+        public uint Flags;             // SpriteFlipX | SpriteFlipY | SpriteReplace
+    }
+    public const uint SpriteFlipX = 1, SpriteFlipY = 2, SpriteReplace = 4;
+    [DllImport(Lib)] public static extern int rc2dgi_sprites_device(IntPtr ctx, int which, byte* clearRgba, Atlas* atlas, void* spritesDev, int n, void* countDev, void* statusDev);
+
     // rc2dgi_view: one draw of the display frame (window rectangle, y down; Filter 0 = the texture's own,
     // 1 POINT, 2 LINEAR; border A == 0: none)
     [StructLayout(LayoutKind.Sequential)]

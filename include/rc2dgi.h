@@ -717,6 +717,77 @@ int rc2dgi_paint_device(rc2dgi_ctx *ctx, int which, const unsigned char *clear_r
                         const void *count_dev, void *status_dev);
 int rc2dgi_paint_device_limits(const rc2dgi_config *cfg, int *batch_prims, long long *work_bytes);
 
+/* ---- a sprite list in device memory, drawn from one atlas image, enqueued on the context stream.  (The textured draws
+ * of a game that lights its world with this library: walls with albedo into colorRT, light cookies and glowing
+ * particles into emissiveRT -- raylib's DrawTextureRec(atlas, source, position, tint) into the render texture, hundreds
+ * to tens of thousands of times a frame, in one call instead of one rc2dgi_write_device launch a sprite.)  The values
+ * are rc2dgi_write's, the list is rc2dgi_paint_device's.
+ *   atlas      a host struct, read during the call: `dev` an image of w x h pixels (1 .. 32768 each) on the context's
+ *              device whose row 0 is the TOP row (image order, y down), in `format` RC2DGI_FMT_RGBA8, _RGBA16F or
+ *              _RGBA32F; pitch_bytes == 0 is a tight row, otherwise it is at least a row and a multiple of a pixel
+ *              (4 / 8 / 16 bytes); `dev` is aligned to a pixel.  The atlas must not overlap the context's textures.
+ *   sprites_dev  n records of rc2dgi_sprite (32 bytes, eight 32-bit words each) on the context's device, aligned to 4
+ *              bytes; 0 <= n <= 1 << 20.  n == 0 admits a null sprites_dev.
+ *   which, clear_rgba, count_dev, status_dev   as for rc2dgi_paint_device: RC2DGI_RT_COLOR or RC2DGI_RT_EMISSIVE; an
+ *              optional ClearBackground colour that belongs to the first batch; NULL or one int32 on the device, read on
+ *              the stream when the work runs, the number drawn being m = min(max(*count_dev, 0), n), or n with NULL
+ *              (m == 0 with a clear colour is a clear only, m == 0 without one leaves the texture as it is); NULL or
+ *              two int32 on the device that receive {m, refused} on the stream on every call, m == 0 included.
+ *   Pixels     sprite k covers the screen pixels (dx + i, dy + j), 0 <= i < w, 0 <= j < h, in raylib screen coordinates
+ *              (y down) as rc2dgi_paint, clipped to the W x H target.  Screen pixel (X, Y) is texel (X, H - 1 - Y) of
+ *              the texture, which is in GL order.  Its source is atlas pixel (sx + i', sy + j') with
+ *              i' = RC2DGI_SPRITE_FLIP_X ? w - 1 - i : i and j' = RC2DGI_SPRITE_FLIP_Y ? h - 1 - j : j.  That is 1:1 and
+ *              POINT: the library's statement of an unscaled, unrotated DrawTextureRec at an integer position; like
+ *              the scaled views of rc2dgi_compose it has not been probed against a GL implementation.  A sprite wholly
+ *              off the target draws nothing and is not refused.
+ *   Values     `value` is what rc2dgi_write makes of that pixel for the atlas format and the context's storage (its
+ *              "Values" paragraph, unchanged).  The tint channel is t = (float)k / 255.0f in F32 and F16 storage and
+ *              (float)k * (1.0f / 255.0f) in RGBA8_COMPAT storage (white is exactly 1.0f in both), and
+ *              src.c = value.c * t.c, one single multiply a channel, alpha included.  Without RC2DGI_SPRITE_REPLACE the
+ *              texel becomes blend(src, texel), the SRC_ALPHA / ONE_MINUS_SRC_ALPHA blend of
+ *              rc2dgi_write(.., RC2DGI_WRITE_BLEND) in the context's storage; with it the texel becomes src in float
+ *              storage and q8(src) * (1/255) in RGBA8_COMPAT storage.  So a white-tinted sprite that lies inside the
+ *              target leaves the bits rc2dgi_write_device leaves for the same sub-image with RC2DGI_WRITE_FLIP (image
+ *              row 0 is the top), and with RC2DGI_WRITE_BLEND unless RC2DGI_SPRITE_REPLACE is set.
+ *   Draw order the sprites are applied in list order on every texel, across batches too.
+ *   Refused    the device cannot fail a call, so a refused sprite draws nothing and is counted in `refused`; the other
+ *              sprites are unaffected.  With AW x AH the atlas size, a sprite is refused when
+ *                flags & ~7 != 0, or
+ *                w < 1, h < 1, sx < 0, sy < 0, w > AW - sx or h > AH - sy (compared in this form), or
+ *                dx or dy is outside [-2^22, 2^22].
+ *              Nothing read from sprites_dev or count_dev becomes an address, an index or a loop bound before it has
+ *              passed this test or that clamp and the sprite's pixel box has been clipped to the target: a buffer of
+ *              garbage draws nothing and faults nothing.
+ *   Order      the call is enqueued behind whatever is in flight on the context stream and returns; it does not wait
+ *              for the stream or the device (the first call of a context allocates the working memory, the one
+ *              exception).  The caller keeps the list, the count, the status and the atlas alive until rc2dgi_sync()
+ *              and may overwrite the first three on the same stream as soon as the call has returned.  A frame enqueued
+ *              before the call sees the old texels, a frame enqueued after it the new ones.  Drawing into COLOR makes
+ *              COLOR the input again.  Row-strip shards accept the call: the inputs are replicated whole on every rank.
+ *   Memory     the batch capacity and the working bytes are those rc2dgi_paint_device_limits reports: the two calls
+ *              share the context's working memory, whichever runs first allocates it, and the stream order separates
+ *              them.  A list longer than one batch is drawn batch after batch on the stream (three kernels a batch of
+ *              the n given, whatever *count_dev turns out to be).
+ * Errors, each leaving the context valid and the texture untouched: RC2DGI_E_ARG, checked in this order, for a null
+ * context, a bad `which`, n out of range, a null atlas or atlas->dev or a bad atlas size, format, pitch or alignment, a
+ * null sprites_dev with n > 0, a list, count or status pointer not aligned to 4 bytes.  The call only adds an export:
+ * RC2DGI_ABI_VERSION stays 5. */
+typedef struct rc2dgi_atlas {
+  const void *dev; /* device image on the context's device, row 0 = the top row */
+  int w, h;        /* 1 .. 32768 */
+  int pitch_bytes; /* 0 = tight */
+  int format;      /* RC2DGI_FMT_RGBA8 | RC2DGI_FMT_RGBA16F | RC2DGI_FMT_RGBA32F */
+} rc2dgi_atlas;
+typedef struct rc2dgi_sprite {
+  int sx, sy, w, h;         /* source rectangle in the atlas, pixels, y down */
+  int dx, dy;               /* destination of its top-left pixel, raylib screen coordinates (y down) */
+  unsigned char r, g, b, a; /* tint (raylib Color) */
+  unsigned flags;           /* RC2DGI_SPRITE_* */
+} rc2dgi_sprite;
+enum { RC2DGI_SPRITE_FLIP_X = 1, RC2DGI_SPRITE_FLIP_Y = 2, RC2DGI_SPRITE_REPLACE = 4 };
+int rc2dgi_sprites_device(rc2dgi_ctx *ctx, int which, const unsigned char *clear_rgba, const rc2dgi_atlas *atlas,
+                          const void *sprites_dev, int n, const void *count_dev, void *status_dev);
+
 /* ---- row-strip sharding of one frame over `world` ranks.
  * rc2dgi_set_shard: the context computes screen rows [rank*H/world, (rank+1)*H/world) of the
  * merged colorRT / tempRT and exactly what they depend on (world = 1: the whole frame again).

@@ -55,4 +55,14 @@ hipError_t paint_prims_device(float4 *dst, int W, int H, int pitch, bool u8, con
                               const void *prims_dev, int n, const void *count_dev, void *status_dev,
                               PaintDevBuffers &buf, hipStream_t st);
 
+// The steps rc2dgi_sprites_device (rc2dgi_sprites.hip) runs unchanged on the same working memory.
+// ClearBackground(clear) as a texel (zero without a clear colour).
+float4 paint_dev_clear(const unsigned char *clear, bool u8);
+// k_paint_dev_bin over the nb records of the batch at `base`.  recs: `batch` records of 48 bytes that begin as
+// PaintPrim does -- the clipped pixel box in words 0 .. 3, word 5 (ntri) positive when the record draws.
+void paint_dev_enqueue_bin(const void *recs, int n, const int *count_dev, int base, int nb, const PaintDevPlan &plan,
+                           unsigned *masks, hipStream_t st);
+// k_paint_dev_finish: {m, refused} to `status` (null: nothing) and the refusal counter, counters[0], back to zero.
+void paint_dev_enqueue_finish(unsigned *counters, const int *count_dev, int n, int *status, hipStream_t st);
+
 }  // namespace rc2dgi

@@ -41,16 +41,6 @@ struct PaintXform {  // to_window's constants, computed on the host as to_window
   int W, H;
 };
 
-// the number of primitives of the batch at `base`: m = min(max(*count_dev, 0), n) of the call, then this batch's share
-__device__ __forceinline__ int paint_dev_total(const int *__restrict__ count_dev, int n) {
-  if (!count_dev) return n;
-  const int c = *count_dev;
-  return min(max(c, 0), n);
-}
-__device__ __forceinline__ int paint_dev_batch(const int *__restrict__ count_dev, int n, int base, int batch) {
-  return min(max(paint_dev_total(count_dev, n) - base, 0), batch);
-}
-
 struct PaintSnap {
   long long x, y;
 };
@@ -263,6 +253,28 @@ PaintDevPlan paint_dev_plan(int W, int H) {
   return p;
 }
 
+float4 paint_dev_clear(const unsigned char *clear, bool u8) {
+  if (clear && u8)  // ClearBackground into RGBA8: the texel is c itself, read as c * (1/255)
+    return make_float4((float)clear[0] * kInv255, (float)clear[1] * kInv255, (float)clear[2] * kInv255,
+                       (float)clear[3] * kInv255);
+  if (clear)  // ClearBackground: rlClearColor(c / 255)
+    return make_float4((float)clear[0] / 255.0f, (float)clear[1] / 255.0f, (float)clear[2] / 255.0f,
+                       (float)clear[3] / 255.0f);
+  return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+void paint_dev_enqueue_bin(const void *recs, int n, const int *count_dev, int base, int nb, const PaintDevPlan &plan,
+                           unsigned *masks, hipStream_t st) {
+  int th_shift = 0;
+  while ((1 << th_shift) < plan.tile_h) ++th_shift;
+  hipLaunchKernelGGL(k_paint_dev_bin, dim3((nb + 3) / 4), dim3(256), 0, st, static_cast<const PaintPrim *>(recs), n,
+                     count_dev, base, plan.batch, masks, plan.tiles_x, th_shift);
+}
+
+void paint_dev_enqueue_finish(unsigned *counters, const int *count_dev, int n, int *status, hipStream_t st) {
+  hipLaunchKernelGGL(k_paint_dev_finish, dim3(1), dim3(1), 0, st, counters, count_dev, n, status);
+}
+
 void PaintDevBuffers::release() {
   if (work) (void)hipFree(work);
   work = nullptr;
@@ -288,15 +300,7 @@ hipError_t paint_prims_device(float4 *dst, int W, int H, int pitch, bool u8, con
   paint_circle_table(tab.c, tab.s);
   // to_window's constants (rc2dgi_paint.hip), evaluated here as it evaluates them
   const PaintXform xf{2.0f / (float)W, 2.0f / (float)(-H), (float)W * 0.5f, (float)H * 0.5f, W, H};
-  float4 cl = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if (clear && u8)  // ClearBackground into RGBA8: the texel is c itself, read as c * (1/255)
-    cl = make_float4((float)clear[0] * kInv255, (float)clear[1] * kInv255, (float)clear[2] * kInv255,
-                     (float)clear[3] * kInv255);
-  else if (clear)  // ClearBackground: rlClearColor(c / 255)
-    cl = make_float4((float)clear[0] / 255.0f, (float)clear[1] / 255.0f, (float)clear[2] / 255.0f,
-                     (float)clear[3] / 255.0f);
-  int th_shift = 0;
-  while ((1 << th_shift) < plan.tile_h) ++th_shift;
+  const float4 cl = paint_dev_clear(clear, u8);
   // the batches follow each other on the stream: batch b + 1 blends over what batch b left, so the draw order holds
   const int batches = n == 0 ? (clear ? 1 : 0) : (n + plan.batch - 1) / plan.batch;
   for (int b = 0; b < batches; ++b) {
@@ -305,8 +309,7 @@ hipError_t paint_prims_device(float4 *dst, int W, int H, int pitch, bool u8, con
       hipLaunchKernelGGL(k_paint_dev_setup, dim3((nb + 255) / 256), dim3(256), 0, st,
                          static_cast<const unsigned *>(prims_dev), n, cnt, base, plan.batch, prims, tris, counters, xf,
                          tab);
-      hipLaunchKernelGGL(k_paint_dev_bin, dim3((nb + 3) / 4), dim3(256), 0, st, static_cast<const PaintPrim *>(prims),
-                         n, cnt, base, plan.batch, masks, plan.tiles_x, th_shift);
+      paint_dev_enqueue_bin(prims, n, cnt, base, nb, plan, masks, st);
     }
     hipLaunchKernelGGL(k_paint_dev_raster, dim3(plan.tiles_x, plan.tiles_y), dim3(256), 0, st, dst, W, H, pitch,
                        clear && b == 0 ? 1 : 0, cl, static_cast<const PaintPrim *>(prims),
@@ -315,7 +318,7 @@ hipError_t paint_prims_device(float4 *dst, int W, int H, int pitch, bool u8, con
     if (e != hipSuccess) return e;
   }
   if (n > 0 || status_dev) {
-    hipLaunchKernelGGL(k_paint_dev_finish, dim3(1), dim3(1), 0, st, counters, cnt, n, static_cast<int *>(status_dev));
+    paint_dev_enqueue_finish(counters, cnt, n, static_cast<int *>(status_dev), st);
     e = hipGetLastError();
   }
   return e;

@@ -30,3 +30,31 @@ struct WriteArgs {
 hipError_t launch_write(const WriteArgs &a, int format, bool u8, bool blend, hipStream_t st);
 
 }  // namespace rc2dgi
+
+#ifdef __HIP__  // device units only (rc2dgi_write.hip, rc2dgi_sprites.hip): the one definition of a pixel's value
+#include "rc2dgi_device.h"
+
+namespace rc2dgi {
+
+template <int FMT> struct WritePixel;
+template <> struct WritePixel<RC2DGI_FMT_RGBA32F> { typedef uint4 T; };
+template <> struct WritePixel<RC2DGI_FMT_RGBA16F> { typedef uint2 T; };
+template <> struct WritePixel<RC2DGI_FMT_RGBA8> { typedef unsigned T; };
+
+// the value a pixel becomes in a texture whose storage is RGBA8_COMPAT (U8) or float (include/rc2dgi.h)
+template <bool U8, int FMT>
+__device__ __forceinline__ float4 write_value(typename WritePixel<FMT>::T p) {
+  if constexpr (FMT == RC2DGI_FMT_RGBA8) {
+    const float r = (float)(p & 255u), g = (float)((p >> 8) & 255u), b = (float)((p >> 16) & 255u), a = (float)(p >> 24);
+    return U8 ? make_float4(r * kInv255, g * kInv255, b * kInv255, a * kInv255)
+              : make_float4(r / 255.0f, g / 255.0f, b / 255.0f, a / 255.0f);
+  } else {
+    float4 v;
+    if constexpr (FMT == RC2DGI_FMT_RGBA16F) v = GiF16::unpack(p);
+    else v = make_float4(__uint_as_float(p.x), __uint_as_float(p.y), __uint_as_float(p.z), __uint_as_float(p.w));
+    return U8 ? GiU8::unpack(GiU8::pack(v)) : v;
+  }
+}
+
+}  // namespace rc2dgi
+#endif

@@ -53,6 +53,23 @@ class Prim(ctypes.Structure):
                 ("a", ctypes.c_ubyte)]
 
 
+class Atlas(ctypes.Structure):
+    """rc2dgi_atlas: a device image of w x h pixels (row 0 = the top row) that rc2dgi_sprites_device draws from;
+    pitch_bytes 0 is a tight row; format FMT_RGBA8 / FMT_RGBA16F / FMT_RGBA32F."""
+    _fields_ = [("dev", ctypes.c_void_p), ("w", ctypes.c_int), ("h", ctypes.c_int), ("pitch_bytes", ctypes.c_int),
+                ("format", ctypes.c_int)]
+
+
+class Sprite(ctypes.Structure):
+    """rc2dgi_sprite (32 bytes): the source rectangle (sx, sy, w, h) of the atlas, drawn 1:1 with its top-left pixel
+    at (dx, dy) in raylib screen coordinates, a tint and SPRITE_* flags."""
+    _fields_ = [("sx", ctypes.c_int), ("sy", ctypes.c_int), ("w", ctypes.c_int), ("h", ctypes.c_int),
+                ("dx", ctypes.c_int), ("dy", ctypes.c_int), ("r", ctypes.c_ubyte), ("g", ctypes.c_ubyte),
+                ("b", ctypes.c_ubyte), ("a", ctypes.c_ubyte), ("flags", ctypes.c_uint)]
+
+
+SPRITE_FLIP_X, SPRITE_FLIP_Y, SPRITE_REPLACE = 1, 2, 4
+
 FILTER_RT, FILTER_POINT, FILTER_LINEAR = 0, 1, 2
 MAX_VIEWS = 16
 RED = (230, 41, 55, 255)  # raylib Color.Red, the thumbnails' border (RC2DGI.cs:435-448)
@@ -283,6 +300,8 @@ def load_library(path: Optional[str] = None):
         "rc2dgi_paint_device": ([vp, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), vp, ctypes.c_int, vp, vp],
                                 ctypes.c_int),
         "rc2dgi_paint_device_limits": ([ctypes.POINTER(_Config), ip, ctypes.POINTER(ctypes.c_longlong)], ctypes.c_int),
+        "rc2dgi_sprites_device": ([vp, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(Atlas), vp,
+                                   ctypes.c_int, vp, vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -456,6 +475,16 @@ class RC2DGI:
         cl = None if clear is None else (ctypes.c_ubyte * 4)(*[int(v) for v in clear])
         self._check(self._L.rc2dgi_paint(self._h, RT[which], cl, arr, len(prims)), f"paint {which}")
 
+    def _dev_i32(self, call, t, what, numel=None):
+        """the address of a contiguous int32 tensor on this context's GPU (a list, a count or a status of `call`)"""
+        if not getattr(t, "is_cuda", False) or t.device.index != self.device:
+            raise TypeError(f"{call}: {what}: expected a tensor on this context's GPU")
+        if str(t.dtype) != "torch.int32" or not t.is_contiguous():
+            raise TypeError(f"{call}: {what}: expected a contiguous int32 tensor")
+        if numel is not None and t.numel() != numel:
+            raise ValueError(f"{call}: {what}: expected {numel} element(s), got {t.numel()}")
+        return ctypes.c_void_p(t.data_ptr())
+
     def paint_device(self, which, prims, clear=None, count=None, status=None) -> None:
         """The same painting from a primitive list in device memory, enqueued on the context stream
         (rc2dgi_paint_device): nothing waits.  prims: a contiguous torch.int32 (n, 6) tensor on this context's GPU, a row
@@ -465,16 +494,7 @@ class RC2DGI:
         counted in `refused`.  Keep the tensors alive until sync(); they may be overwritten on the same stream as soon
         as the call has returned."""
         w = RT[which] if isinstance(which, str) else int(which)
-
-        def dev_i32(t, what, numel=None):
-            if not getattr(t, "is_cuda", False) or t.device.index != self.device:
-                raise TypeError(f"paint_device: {what}: expected a tensor on this context's GPU")
-            if str(t.dtype) != "torch.int32" or not t.is_contiguous():
-                raise TypeError(f"paint_device: {what}: expected a contiguous int32 tensor")
-            if numel is not None and t.numel() != numel:
-                raise ValueError(f"paint_device: {what}: expected {numel} element(s), got {t.numel()}")
-            return ctypes.c_void_p(t.data_ptr())
-
+        dev_i32 = lambda t, what, numel=None: self._dev_i32("paint_device", t, what, numel)  # noqa: E731
         p = dev_i32(prims, "prims")
         if prims.dim() != 2 or prims.shape[1] != 6:
             raise ValueError(f"paint_device: expected (n, 6) words, got {tuple(prims.shape)}")
@@ -484,6 +504,35 @@ class RC2DGI:
                                                 None if count is None else dev_i32(count, "count", 1),
                                                 None if status is None else dev_i32(status, "status", 2)),
                     f"paint_device {which}")
+
+    def sprites_device(self, which, atlas, sprites, clear=None, count=None, status=None) -> None:
+        """A sprite list in device memory drawn from one atlas image, enqueued on the context stream
+        (rc2dgi_sprites_device): nothing waits.  atlas: a (AH, AW, 4) uint8, float16 or float32 tensor on this
+        context's GPU with contiguous pixels, row 0 the top row (its row stride is the pitch, so a view of a larger
+        tensor is accepted); sprites: a contiguous torch.int32 (n, 8) tensor, a row the eight words of rc2dgi_sprite
+        (pack_sprites makes one); clear, count and status as for paint_device.  Each sprite is drawn 1:1 at its integer
+        position, tinted, and blended over the texels (SPRITE_REPLACE: replaces them) with write()'s values; a sprite
+        the header's rule refuses draws nothing and is counted in status[1].  Keep the tensors alive until sync()."""
+        w = RT[which] if isinstance(which, str) else int(which)
+        dev_i32 = lambda t, what, numel=None: self._dev_i32("sprites_device", t, what, numel)  # noqa: E731
+        if not getattr(atlas, "is_cuda", False) or atlas.device.index != self.device:
+            raise TypeError("sprites_device: atlas: expected a tensor on this context's GPU")
+        fmt = _READ_FORMATS.get(str(atlas.dtype).replace("torch.", ""))
+        if fmt is None:
+            raise TypeError("sprites_device: atlas: expected a float32, float16 or uint8 tensor")
+        if atlas.dim() != 3 or atlas.shape[2] != 4 or atlas.stride(2) != 1 or atlas.stride(1) != 4:
+            raise ValueError(f"sprites_device: atlas: expected (AH, AW, 4) with contiguous pixels, got {tuple(atlas.shape)}")
+        ah, aw = int(atlas.shape[0]), int(atlas.shape[1])
+        a = Atlas(atlas.data_ptr(), aw, ah, int(atlas.stride(0)) * atlas.element_size() if ah > 1 else 0, fmt)
+        p = dev_i32(sprites, "sprites")
+        if sprites.dim() != 2 or sprites.shape[1] != 8:
+            raise ValueError(f"sprites_device: expected (n, 8) words, got {tuple(sprites.shape)}")
+        n = int(sprites.shape[0])
+        cl = None if clear is None else (ctypes.c_ubyte * 4)(*[int(v) for v in clear])
+        self._check(self._L.rc2dgi_sprites_device(self._h, w, cl, ctypes.byref(a), p if n else None, n,
+                                                  None if count is None else dev_i32(count, "count", 1),
+                                                  None if status is None else dev_i32(status, "status", 2)),
+                    f"sprites_device {which}")
 
     def download(self, which: str, dtype=np.float32) -> np.ndarray:
         w = RT[which]
@@ -947,6 +996,29 @@ def pack_prims(kind, xywh, rgba):
         raise ValueError(f"pack_prims: rgba is ({n}, 4) uint8, got {tuple(rgba.shape)} {rgba.dtype}")
     return torch.cat([kind.reshape(n, 1).to(torch.int32), xywh.contiguous().view(torch.int32),
                       rgba.contiguous().view(torch.int32)], dim=1)
+
+
+def pack_sprites(src_xywh, dst_xy, tint=None, flags=None):
+    """The (n, 8) int32 tensor RC2DGI.sprites_device takes, with torch ops alone on the inputs' device (nothing
+    waits): src_xywh (n, 4) int32, the source rectangles of the atlas; dst_xy (n, 2) int32, where each top-left pixel
+    goes (raylib screen coordinates); tint (n, 4) uint8, None: white; flags (n,) of any integer dtype (SPRITE_*), None:
+    0.  The four tint bytes go little-endian into word 6, as rc2dgi_sprite lays them out."""
+    import torch
+
+    if src_xywh.dim() != 2 or src_xywh.shape[1] != 4 or src_xywh.dtype != torch.int32:
+        raise ValueError(f"pack_sprites: src_xywh is (n, 4) int32, got {tuple(src_xywh.shape)} {src_xywh.dtype}")
+    n = int(src_xywh.shape[0])
+    if tuple(dst_xy.shape) != (n, 2) or dst_xy.dtype != torch.int32:
+        raise ValueError(f"pack_sprites: dst_xy is ({n}, 2) int32, got {tuple(dst_xy.shape)} {dst_xy.dtype}")
+    if tint is None:
+        tint = torch.full((n, 4), 255, dtype=torch.uint8, device=src_xywh.device)
+    if tuple(tint.shape) != (n, 4) or tint.dtype != torch.uint8:
+        raise ValueError(f"pack_sprites: tint is ({n}, 4) uint8, got {tuple(tint.shape)} {tint.dtype}")
+    if flags is None:
+        flags = torch.zeros(n, dtype=torch.int32, device=src_xywh.device)
+    if tuple(flags.shape) != (n,) or flags.dtype.is_floating_point or flags.dtype == torch.bool:
+        raise ValueError(f"pack_sprites: flags is ({n},) of an integer dtype, got {tuple(flags.shape)} {flags.dtype}")
+    return torch.cat([src_xywh, dst_xy, tint.contiguous().view(torch.int32), flags.reshape(n, 1).to(torch.int32)], dim=1)
 
 
 def paint_device_limits(W: int, H: int):

@@ -1,0 +1,715 @@
+"""GPU: rc2dgi_sprites_device -- a device-resident sprite list drawn from one atlas image -- bit for bit against the
+merged code (rc2dgi_write_device one sprite at a time) and against the numpy restatement of the header
+(tests/sprites_ref.py): every atlas format in every storage, lists built to cross every edge of the binning (targets
+that are no multiple of a tile, sprites over and off each side, one over the whole target, 70 over one pixel, the order
+reversed), more than two batches, the device count and status words, each refusal term and a buffer of garbage,
+non-finite texels, the working memory shared with rc2dgi_paint_device, a device-only loop through a frame, a shard, the
+stream order behind a busy device, and the argument errors."""
+import ctypes
+import time
+
+import numpy as np
+import pytest
+
+import sprites_ref as S
+from oracle import paint_ref
+
+pytestmark = pytest.mark.gpu
+
+f32, u32 = np.float32, np.uint32
+SENTINEL = f32([0.375, -2.5, 7.0, 0.625])
+WHITE = (255, 255, 255, 255)
+TARGETS = [(64, 48), (200, 150)]  # no multiple of a tile (64 x 4) in either axis
+AW, AH = 37, 29
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch
+
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    return torch
+
+
+@pytest.fixture(scope="module")
+def R(torch):
+    from radiancecascade2dglobalillumination_amd import rc2dgi
+
+    return rc2dgi
+
+
+# ------------------------------------------------------------------ atlases, textures, calls
+def atlas_np(fmt, aw=AW, ah=AH, seed=1):
+    """(ah, aw, 4) pixels, row 0 the top: bytes, or floats a little outside [0, 1] with alphas from 0 to above 1"""
+    rng = np.random.default_rng(seed)
+    if fmt == "uint8":
+        a = rng.integers(0, 256, (ah, aw, 4)).astype(np.uint8)
+        a[::3, ::2, 3] = 255
+        a[1::5, 1::3, 3] = 0
+        return a
+    a = rng.uniform(-0.25, 1.25, (ah, aw, 4)).astype(f32)
+    a[..., 3] = rng.uniform(-0.1, 1.1, (ah, aw))
+    a[::3, ::2, 3] = 1.0
+    a[1::5, 1::3, 3] = 0.0
+    return a.astype(np.float16) if fmt == "float16" else a
+
+
+def big_atlas_np(fmt, W, H, seed=2):
+    """an atlas larger than the W x H target, so that one sprite covers it"""
+    return atlas_np(fmt, W + 10, H + 7, seed)
+
+
+def to_dev(torch, a, pad=0):
+    """the atlas on the device; pad > 0: a view of an image `pad` pixels wider, a pitch wider than a row"""
+    t = torch.from_numpy(a).to("cuda")
+    if not pad:
+        return t
+    wide = torch.zeros((a.shape[0], a.shape[1] + pad, 4), dtype=t.dtype, device="cuda")
+    wide[:, :a.shape[1]] = t
+    return wide[:, :a.shape[1]]
+
+
+def base_texture(W, H, seed=5):
+    rng = np.random.default_rng(seed)
+    return rng.uniform(0.0, 1.0, (H, W, 4)).astype(f32)
+
+
+def texture(ctx, which, u8):
+    return ctx.download(which, np.uint8) if u8 else ctx.download(which)
+
+
+def draw(torch, ctx, which, atlas_t, wd, clear=None, count=None):
+    """sprites_device of (n, 8) words; returns the status words"""
+    t = torch.from_numpy(np.ascontiguousarray(wd, np.int32).reshape(-1, 8)).to("cuda")
+    status = torch.full((2,), -77, dtype=torch.int32, device="cuda")
+    cnt = None if count is None else torch.tensor([count], dtype=torch.int32, device="cuda")
+    ctx.sprites_device(which, atlas_t, t, clear, cnt, status)
+    ctx.sync()
+    return status.cpu().numpy().tolist()
+
+
+def differing(got, want):
+    return f"{np.count_nonzero(np.any(got != want, axis=-1))} texels differ"
+
+
+def rand_tint(rng):
+    return tuple(int(v) for v in rng.integers(0, 256, 4))
+
+
+# ------------------------------------------------------------------ 1. against the merged code
+def inside_list(W, H, aw, ah, n, seed, flags):
+    """n white sprites wholly inside the target, 1 x 1 up to 40 x 30 (or the atlas), overlapping"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(n):
+        w = int(rng.integers(1, min(40, aw, W) + 1)) if k > 3 else (1, min(40, aw, W))[k % 2]
+        h = int(rng.integers(1, min(30, ah, H) + 1)) if k > 3 else (1, min(30, ah, H))[k // 2]
+        out.append((int(rng.integers(0, aw - w + 1)), int(rng.integers(0, ah - h + 1)), w, h,
+                    int(rng.integers(0, W - w + 1)), int(rng.integers(0, H - h + 1)), WHITE, flags))
+    return out
+
+
+@pytest.mark.parametrize("replace", [False, True], ids=["blend", "replace"])
+@pytest.mark.parametrize("storage", ["f32", "f16", "rgba8"])
+@pytest.mark.parametrize("fmt", ["uint8", "float16", "float32"])
+@pytest.mark.parametrize("W,H,pitched", [(200, 150, False), (64, 48, True)])
+def test_white_sprites_equal_write_device_one_by_one(R, torch, W, H, pitched, fmt, storage, replace):
+    """the header's consequence: a white sprite inside the target is rc2dgi_write_device of the sub-image with FLIP, and
+    with BLEND unless REPLACE.  The pitched atlas is larger than 40 x 30, so that the largest sprites exist."""
+    a = big_atlas_np(fmt, W, H) if pitched else atlas_np(fmt)
+    at = to_dev(torch, a, 6 if pitched else 0)
+    P = inside_list(W, H, a.shape[1], a.shape[0], 200, 11, S.REPLACE if replace else 0)
+    u8 = storage == "rgba8"
+    ctx = R.RC2DGI(W, H, cascade_count=2, storage=storage)
+    twin = R.RC2DGI(W, H, cascade_count=2, storage=storage)
+    for c in (ctx, twin):
+        c.upload("emissive", base_texture(W, H))
+    assert draw(torch, ctx, "emissive", at, S.words(P)) == [200, 0]
+    for sx, sy, w, h, dx, dy, _, _ in P:
+        twin.write("emissive", at[sy:sy + h, sx:sx + w], rect=(dx, H - dy - h, w, h), flip=True, blend=not replace)
+    twin.sync()
+    got, want = texture(ctx, "emissive", u8), texture(twin, "emissive", u8)
+    assert np.array_equal(got.view(u32) if not u8 else got, want.view(u32) if not u8 else want), differing(got, want)
+    assert not np.array_equal(want, texture_of_upload(R, W, H, storage)), "the sprites changed the texture"
+    ctx.close()
+    twin.close()
+
+
+_uploads = {}
+
+
+def texture_of_upload(R, W, H, storage):
+    key = (W, H, storage)
+    if key not in _uploads:
+        c = R.RC2DGI(W, H, cascade_count=2, storage=storage)
+        c.upload("emissive", base_texture(W, H))
+        _uploads[key] = texture(c, "emissive", storage == "rgba8")
+        _uploads[key].setflags(write=False)
+        c.close()
+    return _uploads[key]
+
+
+# ------------------------------------------------------------------ 2. against the restatement
+def edge_list(W, H, aw, ah, seed):
+    """About 300 tinted sprites with every flag combination on a W x H target, from an atlas larger than it: wholly off
+    the target on each side (far and adjacent), over each edge and two corners, one over the whole target, edges on
+    columns 63 / 64 / 128 and on rows that are multiples of 4 from either end, 70 over one pixel."""
+    rng = np.random.default_rng(seed)
+    P = []
+
+    def add(w, h, dx, dy, flags=None):
+        flags = len(P) % 8 if flags is None else flags
+        P.append((int(rng.integers(0, aw - w + 1)), int(rng.integers(0, ah - h + 1)), w, h, dx, dy, rand_tint(rng), flags))
+
+    for dx, dy in ((-40, 3), (W + 5, 3), (3, -40), (3, H + 5), (-20, 3), (W, 3), (3, -20), (3, H)):  # off the target
+        add(20, 20, dx, dy)
+    for dx, dy in ((-7, 5), (W - 9, 5), (5, -6), (5, H - 8), (-3, -3), (W - 4, H - 4)):  # over an edge or a corner
+        for flags in (0, 3, 4):
+            add(20, 15, dx, dy, flags)
+    add(W + 9, H + 6, -4, -3, 0)  # the whole target, blended
+    for x in (63, 64, 128):
+        if x < W:
+            add(9, 5, x, 7)           # its first column on x
+            add(9, 5, x - 8, 13)      # its last column on x
+    for y in (4, 8, H - 4, H - 8):
+        add(11, 6, 30, y)             # its first screen row on y
+        add(11, 6, 41, y - 6)         # its last screen row on y - 1
+        add(70 if W > 70 else 30, 4, 1, y)  # (across a tile column where the target has one)
+    px, py = min(W - 2, 37), min(H - 2, 5)
+    for k in range(70):  # more than 64 over one pixel: the walk crosses the mask's word boundaries
+        w, h = 1 + k % 3, 1 + k % 2
+        add(w, h, px - (k % w), py - (k % h), k % 8)
+    while len(P) < 300:
+        w, h = int(rng.integers(1, 41)), int(rng.integers(1, 31))
+        add(w, h, int(rng.integers(-20, W)), int(rng.integers(-20, H)))
+    order = rng.permutation(len(P))
+    return [P[k] for k in order]
+
+
+@pytest.mark.parametrize("clear", [None, (9, 8, 7, 200)], ids=["noclear", "clear"])
+@pytest.mark.parametrize("storage,fmt", [("f32", "uint8"), ("f32", "float32"), ("rgba8", "uint8"), ("rgba8", "float16")])
+@pytest.mark.parametrize("W,H", TARGETS)
+def test_lists_across_tile_and_word_boundaries_in_both_orders(R, torch, W, H, storage, fmt, clear):
+    a = big_atlas_np(fmt, W, H)
+    at = to_dev(torch, a, 6)
+    P = edge_list(W, H, a.shape[1], a.shape[0], 21)
+    assert len(P) == 300 and {p[7] for p in P} == set(range(8))
+    u8 = storage == "rgba8"
+    ctx = R.RC2DGI(W, H, cascade_count=2, storage=storage)
+    outs = []
+    for reverse in (False, True):
+        ctx.upload("color", base_texture(W, H))
+        start = texture(ctx, "color", u8)
+        wd = S.words(P[::-1] if reverse else P)
+        assert draw(torch, ctx, "color", at, wd, clear) == [300, 0]
+        got, want = texture(ctx, "color", u8), S.draw(start, a, wd, u8, clear)
+        assert np.array_equal(got, want), f"{W}x{H} {storage} {fmt} reversed={reverse}: {differing(got, want)}"
+        outs.append(got)
+    assert not np.array_equal(outs[0], outs[1]), "the two orders give different textures: the order is kept"
+    ctx.close()
+
+
+# ------------------------------------------------------------------ 3. more than two batches
+def test_more_than_two_batches_keep_the_order_and_leave_the_masks_clean(R, torch):
+    W, H = 64, 48
+    batch, _ = R.paint_device_limits(W, H)
+    n = 2 * batch + 70
+    rng = np.random.default_rng(8)
+    a = atlas_np("uint8")
+    at = to_dev(torch, a)
+    wh = rng.integers(1, 4, (n, 2))
+    wd = np.zeros((n, 8), np.int64)
+    wd[:, 2:4] = wh
+    wd[:, 0] = rng.integers(0, AW - 3, n)
+    wd[:, 1] = rng.integers(0, AH - 3, n)
+    wd[:, 4] = rng.integers(-2, W, n)
+    dy = rng.integers(-2, H - 10, n)
+    wd[:, 5] = np.where(dy < 20, dy, dy + 10)  # (screen rows 23 .. 29 are left to the sprites below)
+    wd[:, 6] = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.int64)
+    wd[:, 7] = rng.integers(0, 8, n)
+    for b in (batch, 2 * batch):  # half-transparent sprites straddling each batch boundary, over the same pixels
+        for k in range(b - 3, b + 3):
+            wd[k, 2:6] = [3, 3, 20 + (k - b), 24]
+            wd[k, 6] = (wd[k, 6] & 0xFFFFFF) | (128 << 24)
+            wd[k, 7] = 0
+    wd = (wd & 0xFFFFFFFF).astype(u32).view(np.int32)
+    ctx = R.RC2DGI(W, H, cascade_count=2)
+    ctx.upload("color", base_texture(W, H))
+    start = ctx.download("color")
+    assert draw(torch, ctx, "color", at, wd, (5, 5, 5, 255)) == [n, 0]
+    got, want = ctx.download("color"), S.draw(start, a, wd, False, (5, 5, 5, 255))
+    assert np.array_equal(got, want), differing(got, want)
+    # (the sprites at a batch boundary matter to the result: nothing else touches their rows, and without the first of
+    # the next batch those rows differ)
+    near = wd[batch - 3:batch + 3]
+    assert not np.array_equal(S.draw(start, a, near, False), S.draw(start, a, np.delete(near, 3, axis=0), False))
+    # a following call finds the masks clean: a short list draws itself alone
+    short = wd[5:25]
+    assert draw(torch, ctx, "color", at, short) == [20, 0]
+    got2, want2 = ctx.download("color"), S.draw(want, a, short, False)
+    assert np.array_equal(got2, want2), differing(got2, want2)
+    ctx.close()
+
+
+# ------------------------------------------------------------------ 4. the device count and the status words
+def nine(W, H, seed=3):
+    rng = np.random.default_rng(seed)
+    P = []
+    for k in range(9):
+        w, h = int(rng.integers(4, 31)), int(rng.integers(4, 21))
+        P.append((int(rng.integers(0, AW - w + 1)), int(rng.integers(0, AH - h + 1)), w, h,
+                  int(rng.integers(-5, W - 10)), int(rng.integers(-5, H - 10)), rand_tint(rng), k % 8))
+    return P
+
+
+@pytest.mark.parametrize("storage", ["f32", "rgba8"])
+def test_count_and_status_words(R, torch, storage):
+    W, H, n = 64, 48, 9
+    a = atlas_np("float16")
+    at = to_dev(torch, a)
+    wd = S.words(nine(W, H))
+    u8 = storage == "rgba8"
+    clear = (20, 30, 40, 255)
+    ctx = R.RC2DGI(W, H, cascade_count=2, storage=storage)
+    ctx.upload("color", base_texture(W, H))
+    start = texture(ctx, "color", u8)
+    for count, m in [(-5, 0), (0, 0), (n - 1, n - 1), (n, n), (n + 9, n), (None, n)]:
+        assert draw(torch, ctx, "color", at, wd, clear, count) == [m, 0], count
+        got, want = texture(ctx, "color", u8), S.draw(start, a, wd, u8, clear, m)  # (m == 0: a clear only)
+        assert np.array_equal(got, want), f"count {count}: {differing(got, want)}"
+    # a count torch writes on the stream right before the call, and overwrites right after it has returned
+    stream = torch.cuda.Stream()
+    ctx.set_stream(stream.cuda_stream)
+    with torch.cuda.stream(stream):
+        t = torch.from_numpy(wd).to("cuda")
+        cnt = torch.zeros(1, dtype=torch.int32, device="cuda")
+        status = torch.full((2,), -77, dtype=torch.int32, device="cuda")
+        cnt.fill_(4)
+        ctx.sprites_device("color", at, t, clear, cnt, status)
+        cnt.fill_(-1)
+        t.fill_(0x7FC00000)
+    ctx.sync()
+    assert status.cpu().numpy().tolist() == [4, 0]
+    got, want = texture(ctx, "color", u8), S.draw(start, a, wd, u8, clear, 4)
+    assert np.array_equal(got, want), differing(got, want)
+    ctx.set_stream(None)
+    ctx.close()
+
+
+def test_nothing_to_draw_without_a_clear_leaves_the_texture(R, torch):
+    W, H = 64, 48
+    at = to_dev(torch, atlas_np("uint8"))
+    ctx = R.RC2DGI(W, H, cascade_count=2)
+    start = np.broadcast_to(SENTINEL, (H, W, 4)).copy()
+    ctx.upload("emissive", start)
+    wd = S.words(nine(W, H))
+    none = np.zeros((0, 8), np.int32)
+    for count in (0, -5):
+        assert draw(torch, ctx, "emissive", at, wd, None, count) == [0, 0]
+        assert np.array_equal(ctx.download("emissive").view(u32), start.view(u32))
+    assert draw(torch, ctx, "emissive", at, none) == [0, 0]  # n == 0, a null list
+    assert np.array_equal(ctx.download("emissive").view(u32), start.view(u32))
+    assert draw(torch, ctx, "emissive", at, none, (1, 2, 3, 4)) == [0, 0]  # n == 0: the clear
+    assert np.array_equal(ctx.download("emissive"), np.broadcast_to(f32([1, 2, 3, 4]) / f32(255), (H, W, 4)))
+    ctx.close()
+
+
+# ------------------------------------------------------------------ 5. refused sprites and garbage
+@pytest.mark.parametrize("storage", ["f32", "rgba8"])
+def test_each_refusal_term_draws_nothing_and_is_counted(R, torch, storage):
+    W, H = 64, 48
+    a = atlas_np("uint8")
+    at = to_dev(torch, a)
+    good = nine(W, H)
+    t, big, lim = (250, 10, 10, 255), 2**31 - 1, 1 << 22
+    bad = [(0, 0, 20, 20, 1, 1, t, 8),                 # a flag bit that is not defined
+           (0, 0, 20, 20, 1, 1, t, -(1 << 31)),
+           (0, 0, 0, 20, 1, 1, t, 0),                  # w < 1
+           (0, 0, 20, -3, 1, 1, t, 0),                 # h < 1
+           (-1, 0, 20, 20, 1, 1, t, 0),                # sx < 0
+           (0, -(1 << 31), 20, 20, 1, 1, t, 0),        # sy < 0
+           (AW - 19, 0, 20, 20, 1, 1, t, 0),           # w > AW - sx by one
+           (big, 0, 1, 1, 1, 1, t, 0),                 # w > AW - sx, sx near INT_MAX
+           (0, AH - 19, 20, 20, 1, 1, t, 0),           # h > AH - sy by one
+           (0, big - 3, 20, big, 1, 1, t, 0),
+           (0, 0, 20, 20, lim + 1, 1, t, 0),           # dx = 2^22 + 1
+           (0, 0, 20, 20, -lim - 1, 1, t, 0),
+           (0, 0, 20, 20, 1, lim + 1, t, 0),           # dy
+           (0, 0, 20, 20, 1, -lim - 1, t, 4)]
+    P = []
+    for k, p in enumerate(bad):  # a refused form beside every valid sprite, and at both ends
+        P.append(p)
+        if k < len(good):
+            P.append(good[k])
+    # the limits themselves are accepted (and lie off the target: nothing drawn, nothing refused)
+    edge = [(AW - 20, AH - 20, 20, 20, lim, -lim, t, 7), (0, 0, AW, AH, -lim, lim, t, 0)]
+    P += edge
+    wd = S.words(P)
+    ok = S.accepted(wd, AW, AH)
+    assert np.count_nonzero(~ok) == len(bad) and ok[-2:].all(), "the restated rule refuses exactly the forms above"
+    u8 = storage == "rgba8"
+    ctx = R.RC2DGI(W, H, cascade_count=2, storage=storage)
+    assert draw(torch, ctx, "color", at, wd, (1, 2, 3, 255)) == [len(P), len(bad)]
+    got = texture(ctx, "color", u8)
+    want = S.draw(np.zeros((H, W, 4), np.uint8 if u8 else f32), a, S.words(good), u8, (1, 2, 3, 255))
+    assert np.array_equal(got, want), differing(got, want)
+    ctx.close()
+
+
+@pytest.mark.parametrize("kinds", ["raw", "narrowed"])
+def test_a_buffer_of_garbage_draws_what_the_rule_accepts(R, torch, kinds):
+    """4096 records of seeded random 32-bit words on 64 x 48.  `raw`: as they come (nearly every record is refused).
+    `narrowed`: the same words with the flags cut to 4 bits, the source fields to [-4, 28) and the destinations to
+    [-2^23, 2^23) or, every other record, [-32, 96), so that every term of the rule decides somewhere."""
+    W, H, n = 64, 48, 4096
+    rng = np.random.default_rng(2024)
+    wd = rng.integers(0, 1 << 32, (n, 8), dtype=np.uint64).astype(u32).view(np.int32)
+    if kinds == "narrowed":
+        wd[:, 7] &= 15
+        wd[:, 0:4] = (wd[:, 0:4] & 31) - 4
+        wd[:, 4:6] >>= 8
+        wd[::2, 4:6] = (wd[::2, 4:6] & 127) - 32
+    a = atlas_np("float32")
+    at = to_dev(torch, a)
+    ok = S.accepted(wd, AW, AH)
+    if kinds == "narrowed":
+        assert 100 < np.count_nonzero(ok) < n - 100
+    ctx = R.RC2DGI(W, H, cascade_count=2)
+    status = draw(torch, ctx, "emissive", at, wd, (0, 0, 0, 0))
+    assert status == [n, n - np.count_nonzero(ok)], (status, np.count_nonzero(ok))
+    want = S.draw(np.zeros((H, W, 4), f32), a, wd[ok], False, (0, 0, 0, 0))
+    got = ctx.download("emissive")
+    assert np.array_equal(got, want), differing(got, want)
+    if kinds == "narrowed":
+        assert want.any()
+    # and with a garbage count of its own
+    assert draw(torch, ctx, "emissive", at, wd, (0, 0, 0, 0), count=-(1 << 31)) == [0, 0]
+    assert not ctx.download("emissive").any()
+    assert draw(torch, ctx, "emissive", at, wd, (0, 0, 0, 0), count=(1 << 31) - 1) == status
+    assert np.array_equal(ctx.download("emissive"), want)
+    ctx.close()
+
+
+# ------------------------------------------------------------------ 6. non-finite texels
+def one_nan(x):
+    """the uint32 view with every NaN mapped to one pattern (a NaN's payload is not part of the contract)"""
+    v = np.ascontiguousarray(x, f32).view(u32).copy()
+    v[np.isnan(x)] = 0x7FC00000
+    return v
+
+
+def test_non_finite_texels_propagate_by_ieee_rules(R, torch):
+    W, H = 64, 48
+    a = atlas_np("float32")
+    nan, inf = f32(np.nan), f32(np.inf)
+    a[2, 3] = [nan, 0.5, 0.5, 0.5]
+    a[2, 4] = [0.5, 0.5, 0.5, nan]
+    a[3, 3] = [inf, -inf, 0.25, 0.5]
+    a[3, 4] = [0.25, 0.5, 0.75, inf]
+    a[4, 3] = [0.25, 0.5, 0.75, -inf]
+    a[4, 4] = [inf, inf, inf, 0.0]
+    a[5, 3] = [-inf, nan, inf, 1.0]
+    at = to_dev(torch, a)
+    P = []
+    for k, (tint, flags) in enumerate([(WHITE, 0), (WHITE, 4), ((0, 128, 255, 255), 0), ((255, 255, 255, 0), 0),
+                                       ((0, 0, 0, 0), 4), ((128, 0, 255, 128), 3)]):
+        P.append((1, 1, 8, 8, 3 + 9 * k, 5, tint, flags))           # apart
+        P.append((2, 2, 4, 4, 10 + 2 * k, 30 + k, tint, flags))      # over each other
+    wd = S.words(P)
+    ctx = R.RC2DGI(W, H, cascade_count=2)
+    start = base_texture(W, H)
+    ctx.upload("emissive", start)
+    assert draw(torch, ctx, "emissive", at, wd) == [len(P), 0]
+    got, want = ctx.download("emissive"), S.draw(start, a, wd, False)
+    assert np.isnan(want).any() and np.isinf(want).any()
+    assert np.array_equal(one_nan(got), one_nan(want)), f"{np.count_nonzero(one_nan(got) != one_nan(want))} words differ"
+    ctx.close()
+
+
+# ------------------------------------------------------------------ 7. interplay
+def prims(W, H, seed):
+    """nine translucent rectangles and discs for rc2dgi_paint_device"""
+    rng = np.random.default_rng(seed)
+    P = []
+    for k in range(9):
+        c = tuple(int(v) for v in rng.integers(0, 256, 3)) + (int(rng.integers(60, 255)),)
+        if k % 2:
+            P.append((1, float(rng.uniform(0, W)), float(rng.uniform(0, H)), float(rng.uniform(2, 14)), 0.0) + c)
+        else:
+            P.append((0, float(rng.uniform(-5, W - 10)), float(rng.uniform(-5, H - 10)), float(rng.uniform(4, 30)),
+                      float(rng.uniform(4, 20))) + c)
+    return P
+
+
+def prim_words(R, P):
+    arr = (R.Prim * len(P))()
+    for k, p in enumerate(P):
+        arr[k] = R.Prim(int(p[0]), float(p[1]), float(p[2]), float(p[3]), float(p[4]), *(int(v) for v in p[5:9]))
+    return np.frombuffer(bytes(arr), np.int32).reshape(-1, 6).copy()
+
+
+@pytest.mark.parametrize("storage", ["f32", "rgba8"])
+def test_paint_device_and_sprites_device_share_the_working_memory(R, torch, storage):
+    """paint_device, sprites_device, paint_device on one context, enqueued without a wait between them, equal the
+    restatements composed in that order; then the same with the sprites first, on a fresh context (either call may be
+    the one that allocates)."""
+    W, H = 200, 150
+    u8 = storage == "rgba8"
+    a = atlas_np("uint8")
+    at = to_dev(torch, a)
+    P1, P2, SP = prims(W, H, 31), prims(W, H, 32), nine(W, H, 33) + nine(W, H, 34)
+    w1, w2 = (torch.from_numpy(prim_words(R, P)).to("cuda") for P in (P1, P2))
+    ws = torch.from_numpy(S.words(SP)).to("cuda")
+    st = torch.full((3, 2), -77, dtype=torch.int32, device="cuda")
+    ctx = R.RC2DGI(W, H, cascade_count=2, storage=storage)
+    ctx.paint_device("color", w1, (10, 20, 30, 255), None, st[0])
+    ctx.sprites_device("color", at, ws, None, None, st[1])
+    ctx.paint_device("color", w2, None, None, st[2])
+    ctx.sync()
+    assert st.cpu().numpy().tolist() == [[9, 0], [18, 0], [9, 0]]
+    want = paint_ref.paint(W, H, P1, (10, 20, 30, 255), rgba8=u8)
+    want = S.draw(want, a, S.words(SP), u8)
+    want = paint_ref.paint(W, H, P2, None, base=want, rgba8=u8)
+    got = texture(ctx, "color", u8)
+    assert np.array_equal(got, want), differing(got, want)
+    ctx.close()
+    ctx = R.RC2DGI(W, H, cascade_count=2, storage=storage)
+    ctx.sprites_device("emissive", at, ws, (0, 0, 0, 255), None, st[0])
+    ctx.paint_device("emissive", w1, None, None, st[1])
+    ctx.sprites_device("emissive", at, ws, None, None, st[2])
+    ctx.sync()
+    assert st.cpu().numpy().tolist() == [[18, 0], [9, 0], [18, 0]]
+    want = S.draw(np.zeros((H, W, 4), np.uint8 if u8 else f32), a, S.words(SP), u8, (0, 0, 0, 255))
+    want = S.draw(paint_ref.paint(W, H, P1, None, base=want, rgba8=u8), a, S.words(SP), u8)
+    got = texture(ctx, "emissive", u8)
+    assert np.array_equal(got, want), differing(got, want)
+    ctx.close()
+
+
+@pytest.mark.parametrize("storage", ["f32", "rgba8"])
+def test_device_loop_equals_a_frame_of_the_restated_inputs(R, torch, storage):
+    """torch makes the sprite list on the device, pack_sprites packs it, both inputs are drawn and a frame runs, with
+    no host synchronise between the steps; the merged COLOR equals that of a context given the restated inputs."""
+    W = H = 128
+    u8 = storage == "rgba8"
+    a = atlas_np("uint8")
+    a[..., 3] = np.where(a[..., 3] > 100, 255, 0)  # walls and lights are opaque or absent
+    stream = torch.cuda.Stream()
+    ctx = R.RC2DGI(W, H, cascade_count=3, ray_range=2.0, storage=storage)
+    ctx.set_stream(stream.cuda_stream)
+    with torch.cuda.stream(stream):
+        at = to_dev(torch, a)
+        g = torch.Generator(device="cuda")
+        g.manual_seed(99)
+        n = 24
+        wh = torch.randint(3, 13, (n, 2), generator=g, device="cuda", dtype=torch.int32)
+        sxy = torch.randint(0, AH - 12, (n, 2), generator=g, device="cuda", dtype=torch.int32)
+        dst = torch.randint(-4, W - 4, (n, 2), generator=g, device="cuda", dtype=torch.int32)
+        flags = torch.randint(0, 4, (n,), generator=g, device="cuda")
+        walls = R.pack_sprites(torch.cat([sxy, wh], 1), dst, None, flags)
+        tint = torch.randint(0, 256, (n, 4), generator=g, device="cuda").to(torch.uint8)
+        tint[::2] = 0  # every other sprite is a wall that emits nothing
+        tint[:, 3] = 255
+        lights = R.pack_sprites(torch.cat([sxy, wh], 1), dst, tint, flags)
+        status = torch.zeros((2, 2), dtype=torch.int32, device="cuda")
+        ctx.sprites_device("color", at, walls, (0, 0, 0, 0), None, status[0])
+        ctx.sprites_device("emissive", at, lights, (0, 0, 0, 255), None, status[1])
+        ctx.do_rc2dgi()
+        out = torch.empty((H, W, 4), device="cuda")
+        ctx.read_into(out, "color")
+    ctx.sync()
+    got = out.cpu().numpy()
+    assert status.cpu().numpy().tolist() == [[n, 0], [n, 0]]
+    ww, lw = walls.cpu().numpy(), lights.cpu().numpy()
+    ctx.set_stream(None)
+    ctx.close()
+    zero = np.zeros((H, W, 4), np.uint8 if u8 else f32)
+    color, emissive = S.draw(zero, a, ww, u8, (0, 0, 0, 0)), S.draw(zero, a, lw, u8, (0, 0, 0, 255))
+    assert color.any() and emissive[..., :3].any()
+    b = R.RC2DGI(W, H, cascade_count=3, ray_range=2.0, storage=storage)
+    b.frame(color, emissive)
+    b.sync()
+    want = b.download("color")
+    b.close()
+    assert np.array_equal(got.view(u32), want.view(u32)), differing(got, want)
+
+
+def test_a_row_strip_shard_accepts_the_call(R, torch):
+    W, H = 96, 64
+    a = atlas_np("float32")
+    at = to_dev(torch, a)
+    wd = S.words(nine(W, H))
+    ctx = R.RC2DGI(W, H, cascade_count=3)
+    ctx.set_shard(0, 2)
+    for which in ("color", "emissive"):
+        assert draw(torch, ctx, which, at, wd, (4, 3, 2, 255)) == [9, 0]
+        got, want = ctx.download(which), S.draw(np.zeros((H, W, 4), f32), a, wd, False, (4, 3, 2, 255))
+        assert np.array_equal(got, want), f"{which}: {differing(got, want)}"
+    ctx.close()
+
+
+# ------------------------------------------------------------------ 8. no wait
+def test_two_sprite_calls_and_a_frame_enqueue_behind_a_busy_device(R, torch):
+    """On a torch stream given to rc2dgi_set_stream, behind a torch.cuda._sleep sized to three times what the
+    synchronising twin's calls took on the host: sprites into COLOR, sprites into EMISSIVE (torch overwrites each list
+    in place as soon as its call has returned), a frame, a read.  The event behind the sleep is unfinished after every
+    call; the frame is the twin's.  One batch a call."""
+    from test_gpu_pipeline import sleep_cycles_per_ms
+
+    W = H = 256
+    a = atlas_np("uint8")
+    cc, ec = (0, 0, 0, 0), (0, 0, 0, 255)
+    rng = np.random.default_rng(77)
+    cw = S.words([(int(rng.integers(0, AW - 12)), int(rng.integers(0, AH - 12)), 12, 12, int(rng.integers(-4, W)),
+                   int(rng.integers(-4, H)), rand_tint(rng), k % 8) for k in range(400)])
+    ew = cw.copy()
+    ew[::2, 6] = np.int32(-(1 << 24))  # every other light is black and opaque
+    assert len(cw) <= R.paint_device_limits(W, H)[0]
+
+    def run(ctx, lib, at, lists):
+        out = torch.full((H, W, 4), -7.0, device="cuda")
+        gi = torch.full(tuple(reversed(ctx.cascade_resolution)) + (4,), -7.0, device="cuda")
+        st = torch.full((2, 2), -77, dtype=torch.int32, device="cuda")
+        lib("sprites_device color", lambda: ctx.sprites_device("color", at, lists[0], cc, None, st[0]))
+        lists[0].fill_(0x7FC00000)
+        lib("sprites_device emissive", lambda: ctx.sprites_device("emissive", at, lists[1], ec, None, st[1]))
+        lists[1].fill_(-1)
+        lib("do", ctx.do_rc2dgi)
+        lib("read_into color", lambda: ctx.read_into(out, "color"))
+        lib("read_into final_gi", lambda: ctx.read_into(gi, "final_gi"))
+        return out, gi, st
+
+    def fresh(stream):
+        ctx = R.RC2DGI(W, H, cascade_count=4)
+        ctx.set_stream(stream.cuda_stream)
+        with torch.cuda.stream(stream):
+            at = to_dev(torch, a)
+            warm = torch.from_numpy(cw).to("cuda")
+            ctx.sprites_device("color", at, warm)  # the first call allocates the working memory: the one wait by design
+            ctx.do_rc2dgi()                        # (the tables)
+        ctx.sync()
+        return ctx, at
+
+    stream = torch.cuda.Stream()
+    twin, at = fresh(stream)
+    with torch.cuda.stream(stream):
+        lists = [torch.from_numpy(cw).to("cuda"), torch.from_numpy(ew).to("cuda")]
+        stream.synchronize()
+
+        def stepwise(name, fn):
+            fn()
+            twin.sync()
+
+        t0 = time.perf_counter()
+        want = run(twin, stepwise, at, lists)
+        twin.sync()
+        twin_seconds = time.perf_counter() - t0
+        want = [t.cpu().numpy() for t in want]
+    twin.set_stream(None)
+    twin.close()
+
+    ctx, at = fresh(stream)
+    rate = sleep_cycles_per_ms(torch, stream)
+    sleep_ms = 3.0 * twin_seconds * 1e3
+    assert sleep_ms < 5000.0, f"the stepwise twin took {twin_seconds:.3f} s on the host"
+    queried = []
+    with torch.cuda.stream(stream):
+        lists = [torch.from_numpy(cw).to("cuda"), torch.from_numpy(ew).to("cuda")]
+        stream.synchronize()
+        plug = torch.cuda.Event()
+        torch.cuda._sleep(int(sleep_ms * rate))
+        plug.record()
+
+        def lib(name, fn):
+            fn()
+            queried.append((name, plug.query()))
+
+        got = run(ctx, lib, at, lists)
+        still_busy = not plug.query()
+    ctx.sync()
+    got = [t.cpu().numpy() for t in got]
+    ctx.set_stream(None)
+    ctx.close()
+    print(f"\nstepwise twin {twin_seconds * 1e3:.2f} ms on the host, sleep {sleep_ms:.2f} ms")
+    waited = [name for name, done in queried if done]
+    assert not waited, f"the plug had run out after {waited[0]}"
+    assert still_busy, "the device was idle before the last call returned"
+    assert got[2].tolist() == [[len(cw), 0], [len(ew), 0]] and want[2].tolist() == got[2].tolist()
+    for k, name in enumerate(("color", "final_gi")):
+        assert np.array_equal(got[k].view(u32), want[k].view(u32)), f"{name} differs from the synchronising twin's"
+    assert not np.array_equal(got[0], np.full_like(got[0], -7.0))
+
+
+# ------------------------------------------------------------------ 9. argument errors
+def test_argument_errors_in_the_documented_order_leave_the_texture(R, torch):
+    W, H = 64, 48
+    ctx = R.RC2DGI(W, H, cascade_count=2)
+    start = np.broadcast_to(SENTINEL, (H, W, 4)).copy()
+    for which in ("color", "emissive"):
+        ctx.upload(which, start)
+    L, h, vp = ctx._L, ctx._h, ctypes.c_void_p
+    at = to_dev(torch, atlas_np("float32"))
+    t = torch.from_numpy(S.words(nine(W, H))).to("cuda")
+    cnt = torch.full((2,), 9, dtype=torch.int32, device="cuda")
+    st = torch.full((4,), -77, dtype=torch.int32, device="cuda")
+    clear = (ctypes.c_ubyte * 4)(255, 255, 255, 255)
+    p, c, s, d = t.data_ptr(), cnt.data_ptr(), st.data_ptr(), at.data_ptr()
+    F32, F16, U8 = R.FMT_RGBA32F, R.FMT_RGBA16F, R.FMT_RGBA8
+    A = lambda dev=d, w=AW, hh=AH, pitch=0, fmt=F32: ctypes.byref(R.Atlas(dev, w, hh, pitch, fmt))  # noqa: E731
+    good = A()
+    bad = [("a bad which", (R.RT["dist"], clear, good, vp(p), 9, vp(c), vp(s))),
+           ("a bad which before a bad n", (-1, clear, good, vp(p), -1, None, None)),
+           ("n < 0", (0, clear, good, vp(p), -1, vp(c), vp(s))),
+           ("n > 1 << 20", (0, clear, good, vp(p), (1 << 20) + 1, vp(c), vp(s))),
+           ("n out of range before a null atlas", (0, clear, None, vp(p), -1, vp(c), vp(s))),
+           ("a null atlas", (0, clear, None, vp(p), 9, vp(c), vp(s))),
+           ("a null atlas before a null list", (0, clear, None, None, 9, vp(c), vp(s))),
+           ("a null atlas image", (1, clear, A(dev=None), vp(p), 9, vp(c), vp(s))),
+           ("an atlas 0 wide", (0, clear, A(w=0), vp(p), 9, vp(c), vp(s))),
+           ("an atlas 32769 tall", (0, clear, A(hh=32769), vp(p), 9, vp(c), vp(s))),
+           ("a bad atlas format", (0, clear, A(fmt=3), vp(p), 9, vp(c), vp(s))),
+           ("a bad atlas format", (0, clear, A(fmt=-1), vp(p), 9, vp(c), vp(s))),
+           ("a pitch smaller than a row", (0, clear, A(pitch=AW * 16 - 16), vp(p), 9, vp(c), vp(s))),
+           ("a pitch that is no multiple of a pixel", (0, clear, A(pitch=AW * 16 + 8), vp(p), 9, vp(c), vp(s))),
+           ("a negative pitch", (0, clear, A(pitch=-16), vp(p), 9, vp(c), vp(s))),
+           ("a misaligned atlas", (0, clear, A(dev=d + 8), vp(p), 9, vp(c), vp(s))),
+           ("a misaligned half atlas", (0, clear, A(dev=d + 4, fmt=F16), vp(p), 9, vp(c), vp(s))),
+           ("a misaligned byte atlas", (0, clear, A(dev=d + 2, fmt=U8), vp(p), 9, vp(c), vp(s))),
+           ("a null list with n > 0", (1, clear, good, None, 9, vp(c), vp(s))),
+           ("a misaligned list", (0, clear, good, vp(p + 2), 8, vp(c), vp(s))),
+           ("a misaligned count", (1, clear, good, vp(p), 9, vp(c + 1), vp(s))),
+           ("a misaligned status", (0, clear, good, vp(p), 9, vp(c), vp(s + 3)))]
+    for what, args in bad:
+        assert L.rc2dgi_sprites_device(h, *args) == -1, what
+        assert L.rc2dgi_last_error(h), what
+    # the order, told by the messages: which, n, the atlas, the list, the alignment
+    for args, word in [((-1, clear, None, None, -1, vp(c + 1), None), b"COLOR"), ((0, clear, None, None, -1, vp(c + 1), None), b"n is"),
+                       ((0, clear, None, None, 9, vp(c + 1), None), b"atlas"), ((0, clear, good, None, 9, vp(c + 1), None), b"null sprite"),
+                       ((0, clear, good, vp(p), 9, vp(c + 1), None), b"aligned to 4")]:
+        assert L.rc2dgi_sprites_device(h, *args) == -1
+        assert word in L.rc2dgi_last_error(h), (word, L.rc2dgi_last_error(h))
+    ctx.sync()
+    assert st.cpu().numpy().tolist() == [-77] * 4, "a refused call writes no status"
+    for which in ("color", "emissive"):
+        assert np.array_equal(ctx.download(which).view(u32), start.view(u32)), which
+    assert L.rc2dgi_sprites_device(h, 0, None, good, None, 0, None, vp(s)) == 0  # n == 0 with a null list
+    most = torch.zeros((1 << 20, 8), dtype=torch.int32, device="cuda")  # the largest n; the count says 9
+    assert L.rc2dgi_sprites_device(h, 0, None, good, vp(most.data_ptr()), 1 << 20, vp(c), vp(s + 8)) == 0
+    ctx.sync()
+    assert st.cpu().numpy().tolist() == [0, 0, 9, 9], "nine records of zeros: w < 1, refused"
+    assert np.array_equal(ctx.download("color").view(u32), start.view(u32))
+    with pytest.raises(TypeError):
+        ctx.sprites_device("color", at, t.cpu())
+    with pytest.raises(TypeError):
+        ctx.sprites_device("color", at.cpu(), t)
+    with pytest.raises(TypeError):
+        ctx.sprites_device("color", at.to(torch.float64), t)
+    with pytest.raises(TypeError):
+        ctx.sprites_device("color", at, t.to(torch.float32))
+    with pytest.raises(ValueError):
+        ctx.sprites_device("color", at[:, :, :3], t)
+    with pytest.raises(ValueError):
+        ctx.sprites_device("color", at, t.reshape(-1, 6))
+    with pytest.raises(ValueError):
+        ctx.sprites_device("color", at, t, status=st)
+    ctx.close()
