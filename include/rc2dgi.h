@@ -632,6 +632,15 @@ int rc2dgi_set_sky_table(rc2dgi_ctx *ctx, const float *rgb, int n);
  *   "strip_tables"    1 (default; f32 storage): row-strip shards build the march's side tables for their own cell rows and exchange
  *                     them with the march field instead of all-gathering distRT; no record texture (see the sharding
  *                     section below); get_tuning "strip_tables_active" tells whether the last frame did
+ *   "paint_plan"      the tile height and the batch of rc2dgi_paint_device and rc2dgi_sprites_device: 0 (default) as the
+ *                     screen size gives them (tiles of 64 x 4 texels and batches of 8192 while a mask of one bit a
+ *                     tile and primitive fits 40 MiB; then tiles of 8 and 16 rows, batches of 4096 and 2048, tiles of
+ *                     32, 64 and 128 rows); otherwise log2(tile_h) | (batch / 2048) << 8 with tile_h 4 .. 128 and batch
+ *                     2048, 4096 or 8192.  RC2DGI_E_ARG for any other value, and for a plan whose masks would exceed
+ *                     40 MiB on this screen (the working memory stays within its 64 MiB).  A set that changes the plan
+ *                     of a context whose working memory exists waits for the context stream and frees that memory;
+ *                     the next of the two calls allocates it again (their one wait).  rc2dgi_paint_device_limits
+ *                     reports the default plan.  get_tuning "paint_tile_h" and "paint_batch": the plan in force
  * rc2dgi_get_tuning also answers "blur_strip_sized" (1: a shard's BLUR / FINAL_GI textures hold its own rows,
  * rc2dgi_device_buffer), "cascade_banded" (1: a shard's GI1 / GI2 hold its band of every direction block,
  * rc2dgi_device_buffer), "rc_variant_count" and "rc_chain_timeouts" (workgroups of the chained

@@ -58,6 +58,7 @@ int rc2dgi_create(const rc2dgi_config *cfg, rc2dgi_ctx **out) {
   c->storage = cfg->storage;
   c->ray_range = cfg->ray_range;
   c->linux_merge = (cfg->flags & RC2DGI_FLAG_LINUX_MERGE_FALLBACK) != 0;
+  c->paint_dev.plan = paint_dev_plan(c->W, c->H);
   int rc = RC2DGI_OK;
   hipError_t e = hipSetDevice(c->device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
@@ -480,6 +481,20 @@ int rc2dgi_set_tuning(rc2dgi_ctx *c, const char *key, int value) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
+  if (fx & kTunePaintPlan) {
+    const PaintDevPlan plan = paint_dev_plan(c->W, c->H, t.paint_plan);
+    if (plan.mask_bytes() > kPaintDevMaskBytes)
+      return fail(c, RC2DGI_E_ARG, "paint_plan: this screen's masks under that plan exceed 40 MiB");
+    const PaintDevPlan &old = c->paint_dev.plan;
+    if (c->paint_dev.work && (plan.tile_h != old.tile_h || plan.batch != old.batch)) {
+      // the masks are laid out by the plan: no painting in flight while the memory goes; the next device call
+      // allocates and zeroes it again
+      HIPCHK(c, hipSetDevice(c->device));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      c->paint_dev.release();
+    }
+    c->paint_dev.plan = plan;
+  }
   static_cast<Tuning &>(*c) = std::move(t);
   if ((fx & kTuneChain) && !c->rc_chain) free_chain(c);
   if (fx & kTuneAlloff) c->alloff.clear();  // (the no-sample proofs divide as the levels do)
@@ -501,6 +516,8 @@ int rc2dgi_get_tuning(rc2dgi_ctx *c, const char *key, int *value) {
       {"blur_strip_sized", c->gwin ? 1 : 0},  // cascadeBlurRT / the copy-back texture hold the own rows (gi_window_apply)
       {"cascade_banded", c->gband ? 1 : 0},   // giRT1 / giRT2 hold the shard's band of every direction block
       {"rc_fill_levels", c->fill_mask},       // levels the last frame wrote as per-block fills (bits)
+      {"paint_tile_h", c->paint_dev.plan.tile_h},  // the device painters' plan in force ("paint_plan")
+      {"paint_batch", c->paint_dev.plan.batch},
   };
   for (const auto &s : state)
     if (k == s.key) {

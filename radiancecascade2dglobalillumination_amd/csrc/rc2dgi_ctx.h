@@ -121,8 +121,9 @@ struct rc2dgi_ctx : rc2dgi::Tuning {
   // row-strip sharding
   RcMapCache rc_maps;  // host-built k_rc_level workgroup maps
   PaintBuffers paint_buf;  // rc2dgi_paint primitive setup
-  PaintDevBuffers paint_dev;  // rc2dgi_paint_device's and rc2dgi_sprites_device's working memory: a fixed size for the
-                              // screen (paint_dev_plan), allocated at the first call of either
+  PaintDevBuffers paint_dev;  // rc2dgi_paint_device's and rc2dgi_sprites_device's plan (paint_dev_plan of the screen
+                              // and the "paint_plan" knob) and working memory: a fixed size for the plan, allocated
+                              // at the first call of either
   unsigned char *present_buf = nullptr;  // rc2dgi_compose's window image (RGBA8), grown on demand
   size_t present_cap = 0;
   unsigned char *query_in = nullptr, *query_out = nullptr;  // rc2dgi_sample / rc2dgi_raycast's points or rays and

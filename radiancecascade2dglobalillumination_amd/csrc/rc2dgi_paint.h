@@ -34,17 +34,23 @@ void paint_circle_table(float cos37[37], float sin37[37]);
 // The plan of a W x H target (host arithmetic only): a tile is 64 x tile_h pixels, a batch `batch` primitives, and the
 // working memory holds, in this order, kPaintDevHead bytes of counters, `batch` set-up records, batch * 36 triangle
 // records and one mask of `batch` bits a tile.
+constexpr size_t kPaintDevMaskBytes = (size_t)40 << 20;  // the masks' share of the 64 MiB the interface promises
 struct PaintDevPlan {
   int tile_h = 4;     // 4 .. 128, a power of two
   int batch = 8192;   // 2048, 4096 or 8192: 64 lanes x (batch / 2048) words x 32 bits
   int tiles_x = 0, tiles_y = 0;
   size_t off_prims = 0, off_tris = 0, off_masks = 0, bytes = 0;
+  size_t mask_bytes() const { return bytes - off_masks; }
 };
-PaintDevPlan paint_dev_plan(int W, int H);
+// code 0: the smallest tiles and the longest batch whose masks fit kPaintDevMaskBytes; otherwise the tile height and
+// the batch of a "paint_plan" code (paint_plan_code_ok, rc2dgi_tuning.h), whatever their masks take: the caller compares
+// mask_bytes() with kPaintDevMaskBytes.
+PaintDevPlan paint_dev_plan(int W, int H, int code = 0);
 
 struct PaintDevBuffers {
-  unsigned char *work = nullptr;  // PaintDevPlan::bytes, allocated at the first call; the masks and counters are zero
-                                  // between calls (the kernels leave them so)
+  PaintDevPlan plan;              // the plan in force (set with the context and by the "paint_plan" knob)
+  unsigned char *work = nullptr;  // plan.bytes, allocated at the first call and laid out by `plan`; the masks and
+                                  // counters are zero between calls (the kernels leave them so)
   void release();
   ~PaintDevBuffers() { release(); }
 };

@@ -30,7 +30,6 @@ namespace {
 
 constexpr int kPaintDevHead = 256;        // bytes of counters ahead of the records: word 0 counts refused primitives
 constexpr int kPaintDevTris = 36;         // triangle slots a primitive (a circle's 18 quads)
-constexpr size_t kPaintDevMaskBytes = (size_t)40 << 20;  // the masks' share of the 64 MiB the interface promises
 
 struct PaintCircle {
   float c[37], s[37];
@@ -236,11 +235,15 @@ __global__ void k_paint_dev_finish(unsigned *__restrict__ counters, const int *_
 
 }  // namespace
 
-PaintDevPlan paint_dev_plan(int W, int H) {
+PaintDevPlan paint_dev_plan(int W, int H, int code) {
   PaintDevPlan p;
   p.tiles_x = (W + 63) / 64;
   auto mask_bytes = [&] { return (size_t)p.tiles_x * (size_t)((H + p.tile_h - 1) / p.tile_h) * (size_t)(p.batch / 8); };
-  while (mask_bytes() > kPaintDevMaskBytes) {  // taller tiles first, then shorter batches, then taller tiles again
+  if (code != 0) {  // (a "paint_plan" code the knob table accepted)
+    p.tile_h = 1 << (code & 255);
+    p.batch = 2048 * (code >> 8);
+  }
+  while (code == 0 && mask_bytes() > kPaintDevMaskBytes) {  // taller tiles first, then shorter batches, then taller tiles
     if (p.tile_h < 16) p.tile_h *= 2;
     else if (p.batch > 2048) p.batch /= 2;
     else p.tile_h *= 2;
@@ -283,9 +286,9 @@ void PaintDevBuffers::release() {
 hipError_t paint_prims_device(float4 *dst, int W, int H, int pitch, bool u8, const unsigned char *clear,
                               const void *prims_dev, int n, const void *count_dev, void *status_dev,
                               PaintDevBuffers &buf, hipStream_t st) {
-  const PaintDevPlan plan = paint_dev_plan(W, H);
+  const PaintDevPlan &plan = buf.plan;
   hipError_t e = hipSuccess;
-  if (!buf.work) {  // the one place the call may wait: the first call's allocation
+  if (!buf.work) {  // the one place the call may wait: the first call's allocation (and the first after a new plan)
     e = hipMalloc(reinterpret_cast<void **>(&buf.work), plan.bytes);
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(buf.work, 0, plan.bytes, st);

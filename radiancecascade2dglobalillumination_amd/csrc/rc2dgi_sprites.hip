@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void k_sprites_raster(float4 *__restrict__ dst
 hipError_t sprites_device(float4 *dst, int W, int H, int pitch, bool u8, const unsigned char *clear,
                           const SpriteAtlas &atlas, const void *sprites_dev, int n, const void *count_dev,
                           void *status_dev, PaintDevBuffers &buf, hipStream_t st) {
-  const PaintDevPlan plan = paint_dev_plan(W, H);
+  const PaintDevPlan &plan = buf.plan;
   static_assert(sizeof(SpriteRec) == 48, "a batch of set-up records fills the PaintPrim region of the plan");
   hipError_t e = hipSuccess;
   if (!buf.work) {  // the one place the call may wait: the first call's allocation (rc2dgi_paint_device's, if it ran)

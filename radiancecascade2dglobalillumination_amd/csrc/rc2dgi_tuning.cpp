@@ -19,6 +19,7 @@ struct Knob {
   bool norm;       // any value, stored as value != 0
   const char *msg;  // the range error
   unsigned effects;
+  bool (*valid)(int) = nullptr;  // non-null: the values accepted besides 0, instead of the range
 };
 
 constexpr int kVariants = INT_MIN;
@@ -57,6 +58,8 @@ const Knob kKnobs[] = {
     {S(rc_chain), 0, 4, kChainHoles, false, "rc_chain is 0 (off), 1 (chain), 2 (unrolled march), 4 (with the top level)",
      kTuneChain | kTuneSideBuffers},
     {S(rc_chain_spin), -1, INT_MAX, 0, false, "rc_chain_spin is -1, 0 or a poll count", 0},
+    {S(paint_plan), 0, 0, 0, false, "paint_plan is 0 or log2(tile_h) 2..7 | (batch / 2048 = 1, 2 or 4) << 8",
+     kTunePaintPlan, paint_plan_code_ok},
     {L(rc_noproof, kLevel), 0, 0, 0, true, "", 0},
     {L(rc_order, kLevel), 0, INT_MAX, 0, false, "rc_order is px | py << 8 | dg << 16", 0},
 };
@@ -126,7 +129,9 @@ bool tuning_set(Tuning &t, int N, int variant_count, const char *key, int value,
   int level = -1;
   const Knob *d = find_knob(key, &level);
   if (!d) return refuse(err, std::string("unknown tuning key ") + (key ? key : ""));
-  if (!d->norm) {
+  if (d->valid) {
+    if (value != 0 && !d->valid(value)) return refuse(err, d->msg);
+  } else if (!d->norm) {
     const int hi = d->hi == kVariants ? variant_count - 1 : d->hi;
     if (value < d->lo || value > hi || (value >= 0 && value < 32 && (d->holes >> value & 1))) return refuse(err, d->msg);
   }

@@ -33,6 +33,7 @@ struct Tuning {
   int rc_pal = 1;         // surface palettes on (where they apply: 4096^2 .. 8192^2 square screens)
   int rc_chain = 0;       // levels N-2 .. 0 in one launch (1; 2: unrolled march; 4: the top level too)
   int rc_chain_spin = 0;  // polls per wait (0 default; -1 diagnostic: all time out)
+  int paint_plan = 0;     // the device painters' tile height and batch (paint_plan_code_ok; 0: by the screen size)
   std::vector<int> rc_variant;  // per level tile shape
   std::vector<int> rc_order;    // per level workgroup order px | py << 8 | dg << 16 (0 = tile-major)
   std::vector<int> rc_tail;     // per level: tail compaction after this many lockstep iterations
@@ -43,6 +44,13 @@ struct Tuning {
 // rc_order code; mode: 0 patches, 1 oriented patches, 2 bands along the rays (rc_logical_order)
 inline int order_code(int px, int py, int dg, int mode = 0) { return px | (py << 8) | (dg << 16) | (mode << 24); }
 
+// paint_plan code: log2(tile_h) | (batch / 2048) << 8 with tile_h 4 .. 128 and batch 2048, 4096 or 8192 (0 is not a
+// code: it asks for the plan the screen size gives, PaintDevPlan in rc2dgi_paint.h)
+inline bool paint_plan_code_ok(int v) {
+  const int th = v & 255, b = v >> 8;
+  return v > 0 && th >= 2 && th <= 7 && (b == 1 || b == 2 || b == 4);
+}
+
 // the per-level vectors at N levels, every level at its default
 void tuning_level_defaults(Tuning &t, int N);
 
@@ -52,6 +60,8 @@ enum TuningEffect : unsigned {
   kTuneChain = 2,        // rc_chain: drain the stream before the value changes; 0 frees the chain
   kTuneAlloff = 4,       // rc_rdiv: the no-sample proofs (alloff) divide as the levels do -- prove them again
   kTuneSideBuffers = 8,  // prepare_side_buffers reads this knob
+  kTunePaintPlan = 16,   // paint_plan: the plan must fit this screen; a changed plan drains the stream and frees the
+                         // painters' working memory
 };
 
 // Set / get `key` on t (N levels; rc_variant takes 0 .. variant_count-1).  The only code that parses keys: a

@@ -29,6 +29,7 @@ KNOB_CASES = [
     ("rc_pal", 0),
     ("rc_chain", 1),
     ("rc_chain_spin", 1000),  # (a positive poll count only: -1 makes every chained wait time out)
+    ("paint_plan", 3 | 1 << 8),  # (tiles of 8 rows, batches of 2048: within 40 MiB of masks on every screen of the tests)
     ("rc_noproof_L<n>", 1),
     ("rc_order_L<n>", 2 | 4 << 8 | 4 << 16),
 ]

@@ -28,6 +28,17 @@ struct Spec {
 };
 
 const int kPatch228 = 2 | 2 << 8 | 8 << 16;  // px | py << 8 | dg << 16
+
+// "paint_plan": 0 or log2(tile_h) | (batch / 2048) << 8, tile_h 4 .. 128, batch 2048, 4096 or 8192 -- every other value
+// between the smallest code and the largest is refused
+std::vector<int> paint_plan_holes() {
+  std::vector<int> holes;
+  for (int v = 1; v < (7 | 4 << 8); ++v) {
+    const int th = v & 255, b = v >> 8;
+    if (!(th >= 2 && th <= 7 && (b == 1 || b == 2 || b == 4))) holes.push_back(v);
+  }
+  return holes;
+}
 const Spec kSpecs[] = {
     {"strip_tables", SCALAR, 1, 1, 0, 1, {}, true},
     {"rc_variant", LEVEL_ALL, 0, 13, 0, kVariantCount - 1, {}, false},
@@ -52,6 +63,7 @@ const Spec kSpecs[] = {
     {"rc_pal", SCALAR, 1, 1, 0, 1, {}, true},
     {"rc_chain", SCALAR, 0, 0, 0, 4, {3}, false},
     {"rc_chain_spin", SCALAR, 0, 0, -1, INT_MAX, {}, false},
+    {"paint_plan", SCALAR, 0, 0, 0, 7 | 4 << 8, paint_plan_holes(), false},
     {"rc_noproof", LEVEL, 0, 0, 0, 1, {}, true},
     {"rc_order", LEVEL, 0, kPatch228, 0, INT_MAX, {}, false},
 };
@@ -174,6 +186,8 @@ void check(int N) {
     refused(t, N, k, 0);
     CHECK(!get(t, N, k, &v), "get '%s' answered", k);
   }
+  // "paint_plan": a code with bits above its two fields is no code
+  for (int v : {2 | 1 << 8 | 1 << 16, 2 | 256 << 8, 3 | 1 << 8 | 1 << 30, INT_MAX, INT_MIN}) refused(t, N, "paint_plan", v);
   // what the C ABI must do on the device after a set
   const struct {
     const char *key;
@@ -183,7 +197,8 @@ void check(int N) {
             {"rc_rdiv", 0, kTuneAlloff},                    {"side_overlap", 1, kTuneSideStream},
             {"rc_pal", 0, kTuneSideBuffers},                {"rc_variant", 1, kTuneSideBuffers},
             {"rc_variant_L0", 1, kTuneSideBuffers},         {"blur_path", 1, 0},
-            {"rc_order_L0", 1, 0},                          {"rc_chain_spin", 5, 0}};
+            {"rc_order_L0", 1, 0},                          {"rc_chain_spin", 5, 0},
+            {"paint_plan", 3 | 2 << 8, kTunePaintPlan},     {"paint_plan", 0, kTunePaintPlan}};
   for (const auto &e : fx) {
     unsigned got = 99;
     CHECK(set(t, N, e.key, e.value, &got) && got == e.effects, "%s: effects %u, expected %u", e.key, got, e.effects);

@@ -98,10 +98,25 @@ def test_fixtures_through_the_device_list(R, torch, case, storage):
 
 
 # ------------------------------------------------------------------ 2. lists across every edge of the binning
-def edge_list(W, H, seed, circles):
+def tile_rows(H, tile_hs):
+    """The screen rows at the cuts of tiles of the heights `tile_hs`: texel rows k * tile_h - 1, k * tile_h and
+    k * tile_h + 1 for the first cut and the last one on the target (the start of a last, perhaps partly covered, tile
+    row), counted from both ends.  Tiles are cut in GL rows: screen row Y is texel row H - 1 - Y."""
+    rows = set()
+    for th in tile_hs:
+        for k in {1, (H - 1) // th}:
+            for g in (k * th - 1, k * th, k * th + 1):
+                if k > 0 and 0 <= g < H:
+                    rows |= {H - 1 - g, g}
+    return sorted(rows)
+
+
+def edge_list(W, H, seed, circles, tile_hs=()):
     """About 300 translucent primitives of both kinds on a W x H target: wholly off the target on each side, one over
     the whole target, negative w / h, radius 0 and below, centres on pixel centres and on tile corners (columns that
-    are multiples of 64, rows that are multiples of 4 from either end), and 70 over one pixel."""
+    are multiples of 64, rows that are multiples of 4 from either end), and 70 over one pixel.  With `tile_hs`, for
+    every row of tile_rows a circle centred on it and a rectangle with an edge on it, on columns that are multiples of
+    64 (tests/test_gpu_paint_plans.py)."""
     rng = np.random.default_rng(seed)
     col = lambda: tuple(int(v) for v in rng.integers(0, 256, 3)) + (int(rng.integers(1, 255)),)  # noqa: E731
     P = []
@@ -120,6 +135,13 @@ def edge_list(W, H, seed, circles):
     centres += [(x + 0.5, y + 0.5) for x in (10.0, 63.0, 64.0) for y in (1.0, 3.0, 4.0)]
     for k, (x, y) in enumerate(centres[:circles]):
         P.append((1, x, y, float(rng.uniform(0.4, 9.0)), 0.0) + col())
+    cols = [float(x) for x in range(0, W + 1, 64)]
+    for k, Y in enumerate(tile_rows(H, tile_hs)):
+        x = cols[k % len(cols)]
+        # a centre on the row's pixel centres or on its upper boundary; a rectangle whose top or bottom edge is that
+        # boundary, across the tile column's cut
+        P.append((1, x + 0.5 * (k % 2), Y + 0.5 * (k // 2 % 2), float(rng.uniform(0.4, 6.0)), 0.0) + col())
+        P.append((0, x - 3.0, float(Y), float(rng.uniform(4, 12)), float(rng.uniform(1, 9)) * (1 - k % 3 % 2 * 2)) + col())
     while len(P) < 300:
         P.append((0, float(rng.uniform(-20, W)), float(rng.uniform(-20, H)), float(rng.uniform(-6, 40)),
                   float(rng.uniform(-6, 30))) + col())

@@ -150,10 +150,11 @@ def texture_of_upload(R, W, H, storage):
 
 
 # ------------------------------------------------------------------ 2. against the restatement
-def edge_list(W, H, aw, ah, seed):
+def edge_list(W, H, aw, ah, seed, rows=()):
     """About 300 tinted sprites with every flag combination on a W x H target, from an atlas larger than it: wholly off
     the target on each side (far and adjacent), over each edge and two corners, one over the whole target, edges on
-    columns 63 / 64 / 128 and on rows that are multiples of 4 from either end, 70 over one pixel."""
+    columns 63 / 64 / 128 and on rows that are multiples of 4 from either end, 70 over one pixel.  With `rows` (screen
+    rows), for each a sprite whose top row and one whose bottom row falls on it (tests/test_gpu_paint_plans.py)."""
     rng = np.random.default_rng(seed)
     P = []
 
@@ -175,6 +176,10 @@ def edge_list(W, H, aw, ah, seed):
         add(11, 6, 30, y)             # its first screen row on y
         add(11, 6, 41, y - 6)         # its last screen row on y - 1
         add(70 if W > 70 else 30, 4, 1, y)  # (across a tile column where the target has one)
+    for k, y in enumerate(rows):
+        x = (60 * k) % max(W - 12, 1)  # (every fifth or so straddles a multiple of 64)
+        add(9, 1 + k % 7, x, y)                  # its first screen row on y
+        add(9, 1 + k % 5, x + 3, y - (k % 5))    # its last screen row on y
     px, py = min(W - 2, 37), min(H - 2, 5)
     for k in range(70):  # more than 64 over one pixel: the walk crosses the mask's word boundaries
         w, h = 1 + k % 3, 1 + k % 2

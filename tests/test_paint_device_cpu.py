@@ -1,5 +1,5 @@
 """CPU: the host-only half of rc2dgi_paint_device (include/rc2dgi.h) -- rc2dgi_paint_device_limits on the screens the
-interface admits, the two exports in the header, the library, C# and ctypes, the null-context refusal, and pack_prims
+interface admits and on both sides of every step of the plan, the two exports in the header, the library, C# and ctypes, the null-context refusal, and pack_prims
 against the byte layout of rc2dgi_prim."""
 import ctypes
 import os
@@ -33,6 +33,50 @@ def test_limits_fit_the_promise(R, W, H):
     assert 0 < work <= 64 << 20
     assert (batch, work) == R.paint_device_limits(W, H)  # a function of the screen size alone
     assert work >= batch * 24  # (it holds at least a batch of set-up records, none smaller than rc2dgi_prim)
+
+
+def plan(W, H):
+    """paint_dev_plan restated from the comments of rc2dgi_paint.h and rc2dgi_paint_dev.hip: (tile_h, batch, bytes).
+    A tile is 64 x tile_h texels with a mask of `batch` bits; from 64 x 4 and 8192 the tile grows to 16 rows, then the
+    batch halves down to 2048, then the tile grows again, while the masks exceed 40 MiB.  The working memory is 256
+    bytes of counters, `batch` set-up records of 48 bytes, 36 triangle slots of 64 bytes a record, and the masks."""
+    tile_h, batch, tiles_x = 4, 8192, (W + 63) // 64
+    masks = lambda: tiles_x * ((H + tile_h - 1) // tile_h) * (batch // 8)  # noqa: E731
+    while masks() > 40 << 20:
+        if tile_h < 16:
+            tile_h *= 2
+        elif batch > 2048:
+            batch //= 2
+        else:
+            tile_h *= 2
+    return tile_h, batch, 256 + batch * 48 + batch * 36 * 64 + masks()
+
+
+# W = 32768 is 512 tile columns, so 40 MiB are 80 tile rows of 8192-bit masks: (H below the step, tile_h, batch there)
+STEPS = [(320, 4, 8192), (640, 8, 8192), (1280, 16, 8192), (2560, 16, 4096), (5120, 16, 2048), (10240, 32, 2048),
+         (20480, 64, 2048), (32768, 128, 2048)]
+
+
+def test_the_restated_plan_steps_where_the_arithmetic_says():
+    """the restatement against the steps worked out by hand: the last height of each plan, the first of the next (one
+    row more starts another tile row) and the height four rows on"""
+    assert plan(64, 48)[:2] == (4, 8192) and plan(1200, 900)[:2] == (4, 8192)
+    for k, (H, th, b) in enumerate(STEPS):
+        assert plan(32768, H)[:2] == (th, b), H
+        if k + 1 < len(STEPS):
+            assert plan(32768, H + 1)[:2] == plan(32768, H + 4)[:2] == STEPS[k + 1][1:], H
+    assert plan(4096, 4096)[:2] == (8, 8192)
+    assert plan(8192, 8192)[:2] == (16, 4096)
+    assert plan(32768, 32768)[:2] == (128, 2048)
+    assert plan(32768, 324)[:2] == (8, 8192) and plan(32768, 644)[:2] == (16, 8192)  # (the GPU tests' natural plans)
+
+
+@pytest.mark.parametrize("W,H", [(32768, H + d) for H, _, _ in STEPS[:-1] for d in (0, 1, 4)] +
+                         [(32768, 1), (4096, 4096), (8192, 8192), (32768, 32768), (4097, 4096), (333, 250), (200, 150)])
+def test_limits_report_the_restated_plan(R, W, H):
+    tile_h, batch, work = plan(W, H)
+    assert R.paint_device_limits(W, H) == (batch, work), (tile_h, batch, work)
+    assert work - (256 + batch * 48 + batch * 36 * 64) <= 40 << 20
 
 
 def test_limits_depend_on_the_screen_size_alone(R):
