@@ -1,7 +1,8 @@
 /* layout.c -- sizeof / offsetof of the ABI structs, as the C compiler lays them out, for
  * tests/test_host_cpu.py to compare with the C# StructLayout(Sequential) mirrors in
  * host/csharp/RC2DGINative.cs (Config, Prim; View: tests/test_present_cpu.py; Ray, RayHit: tests/test_query_cpu.py;
- * Rect, Stats: tests/test_reduce_cpu.py; Tone: tests/test_tone_cpu.py; Atlas, Sprite: tests/test_sprites_cpu.py). */
+ * Rect, Stats: tests/test_reduce_cpu.py; Tone: tests/test_tone_cpu.py; Atlas, Sprite: tests/test_sprites_cpu.py;
+ * SpriteXf: tests/test_sprites_xf_cpu.py). */
 #include <stddef.h>
 #include <stdio.h>
 
@@ -93,5 +94,21 @@ int main(void) {
   F(rc2dgi_sprite, b);
   F(rc2dgi_sprite, a);
   F(rc2dgi_sprite, flags);
+  printf("rc2dgi_sprite_xf %zu\n", sizeof(rc2dgi_sprite_xf));
+  F(rc2dgi_sprite_xf, sx);
+  F(rc2dgi_sprite_xf, sy);
+  F(rc2dgi_sprite_xf, w);
+  F(rc2dgi_sprite_xf, h);
+  F(rc2dgi_sprite_xf, px);
+  F(rc2dgi_sprite_xf, py);
+  F(rc2dgi_sprite_xf, ax);
+  F(rc2dgi_sprite_xf, ay);
+  F(rc2dgi_sprite_xf, bx);
+  F(rc2dgi_sprite_xf, by);
+  F(rc2dgi_sprite_xf, r);
+  F(rc2dgi_sprite_xf, g);
+  F(rc2dgi_sprite_xf, b);
+  F(rc2dgi_sprite_xf, a);
+  F(rc2dgi_sprite_xf, flags);
   return 0;
 }

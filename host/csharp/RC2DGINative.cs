@@ -81,6 +81,23 @@ static unsafe class RC2DGINative
     public const uint SpriteFlipX = 1, SpriteFlipY = 2, SpriteReplace = 4;
     [DllImport(Lib)] public static extern int rc2dgi_sprites_device(IntPtr ctx, int which, byte* clearRgba, Atlas* atlas, void* spritesDev, int n, void* countDev, void* statusDev);
 
+    // rc2dgi_sprites_xf_device: the same list with every sprite scaled, rotated, sheared or mirrored -- DrawTexturePro.
+    // The source rectangle's top-left corner lands on (Px, Py), its top edge becomes the vector (Ax, Ay), its left edge
+    // (Bx, By), in screen pixels (y down); the producer computes them, the device does no trigonometry.  Flags:
+    // SpriteReplace | SpriteLinear (the flips are refused: a mirrored sprite has a negative determinant).
+    [StructLayout(LayoutKind.Sequential, Size = 48)]
+    public struct SpriteXf
+    {
+        public int Sx, Sy, W, H;
+        public float Px, Py;
+        public float Ax, Ay;
+        public float Bx, By;
+        public byte R, G, B, A;        // tint
+        public uint Flags;             // SpriteReplace | SpriteLinear
+    }
+    public const uint SpriteLinear = 8;
+    [DllImport(Lib)] public static extern int rc2dgi_sprites_xf_device(IntPtr ctx, int which, byte* clearRgba, Atlas* atlas, void* spritesDev, int n, void* countDev, void* statusDev);
+
     // rc2dgi_view: one draw of the display frame (window rectangle, y down; Filter 0 = the texture's own,
     // 1 POINT, 2 LINEAR; border A == 0: none)
     [StructLayout(LayoutKind.Sequential)]

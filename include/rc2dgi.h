@@ -797,6 +797,81 @@ enum { RC2DGI_SPRITE_FLIP_X = 1, RC2DGI_SPRITE_FLIP_Y = 2, RC2DGI_SPRITE_REPLACE
 int rc2dgi_sprites_device(rc2dgi_ctx *ctx, int which, const unsigned char *clear_rgba, const rc2dgi_atlas *atlas,
                           const void *sprites_dev, int n, const void *count_dev, void *status_dev);
 
+/* ---- the same list with every sprite scaled, rotated, sheared or mirrored: the source rectangle is mapped onto a
+ * parallelogram of the screen.  (A rotating wall, a swinging door, a spinning light cookie, a zoomed camera -- raylib's
+ * DrawTexturePro(texture, source, dest, origin, rotation, tint), the draw DrawTextureRec is built on.)  There is no
+ * trigonometry on the device: the producer computes the two edge vectors, as rc2dgi_raycast takes a direction as
+ * given.  Everything not restated here is word for word rc2dgi_sprites_device's: `which`, `clear_rgba`, `atlas`,
+ * `count_dev`, `status_dev`, m = min(max(*count_dev, 0), n), the "Order" and "Memory" paragraphs (three kernels a
+ * batch, the working memory rc2dgi_paint_device_limits reports, shared by the three list calls), the shards, and
+ * "drawing into COLOR makes COLOR the input again".
+ *   sprites_dev  n records of rc2dgi_sprite_xf (48 bytes, twelve 32-bit words each) on the context's device, aligned to
+ *              4 bytes; 0 <= n <= 1 << 20.  n == 0 admits a null sprites_dev.
+ *   The record (sx, sy, w, h) is the source rectangle as in rc2dgi_sprite.  Its top-left CORNER (not its first pixel's
+ *              centre) lands on P = (px, py), screen pixels, y down; its whole top edge (+u over w pixels) becomes the
+ *              vector A = (ax, ay), its whole left edge (+v over h pixels) the vector B = (bx, by).  The destination
+ *              is the parallelogram P, P + A, P + A + B, P + B.  Rotation, scale, shear and mirroring are whatever A
+ *              and B say; a mirrored sprite is one with a negative determinant.  flags: RC2DGI_SPRITE_REPLACE (4) and
+ *              RC2DGI_SPRITE_LINEAR (8); RC2DGI_SPRITE_FLIP_X / _FLIP_Y are not accepted in this record.
+ *   Arithmetic every float operation named below is one single fp32 operation, rounded to nearest and not fused
+ *              (a * b + c is two roundings); denormals are kept; divisions are IEEE-correct.  A host that restates
+ *              the rules in float32 gets the device's bits.
+ *   Refused    a refused sprite draws nothing and is counted in `refused`; the others are unaffected.  With AW x AH
+ *              the atlas size, a sprite is refused when
+ *                flags & ~(4 | 8) != 0, or
+ *                w < 1, h < 1, sx < 0, sy < 0, w > AW - sx or h > AH - sy (compared in this form), or
+ *                any c of px, py, ax, ay, bx, by fails fabsf(c) <= 0x1p20f (false for a NaN and an infinity), or
+ *                det = ax * by - ay * bx (two products, one difference) fails fabsf(det) >= 0x1p-20f.
+ *              Nothing read from sprites_dev or count_dev becomes an address, an index or a loop bound before it has
+ *              passed this test or the count's clamp: a buffer of garbage draws nothing and faults nothing.
+ *   Set-up     i00 = by / det, i01 = (-bx) / det, i10 = (-ay) / det, i11 = ax / det.  The x corners are px, px + ax,
+ *              px + bx, (px + ax) + bx, the y corners py, py + ay, py + by, (py + ay) + by; lo / hi are their minimum /
+ *              maximum.  The pixel box is X0 = max((int)floorf(lo_x) - 1, 0), X1 = min((int)floorf(hi_x) + 1, W - 1),
+ *              and Y0, Y1 alike with H.  (With the bounds above every sum is finite and below 2^22: the conversions
+ *              are safe.)  An empty box draws nothing and is not refused.
+ *   The box    is part of the contract: only screen pixels X0 <= X <= X1, Y0 <= Y <= Y1 are ever tested.  For an
+ *              ill-conditioned sprite (a tiny det against large coordinates) the inverse map cancels badly and the
+ *              float test below may pass anywhere; the box confines what such a sprite can touch.
+ *   A pixel    for screen pixel (X, Y) of the box, which is texel (X, H - 1 - Y):
+ *                dxp = ((float)X + 0.5f) - px, dyp = ((float)Y + 0.5f) - py,
+ *                a = dxp * i00 + dyp * i01, b = dxp * i10 + dyp * i11 (two products and one sum each);
+ *              the pixel is covered iff a >= 0 && a < 1 && b >= 0 && b < 1 (a NaN fails).  Then
+ *                s = a * (float)w, t = b * (float)h.
+ *   POINT      (no RC2DGI_SPRITE_LINEAR) the source is atlas pixel (sx + min((int)s, w - 1), sy + min((int)t, h - 1)) and
+ *              `value` is what rc2dgi_write makes of it for the atlas format and the context's storage.
+ *   LINEAR     xs = s - 0.5f, i0 = (int)floorf(xs), fx = xs - (float)i0, and ys, j0, fy alike from t.  The four taps
+ *              are columns clamp(i0, 0, w - 1) and clamp(i0 + 1, 0, w - 1) and rows clamp(j0, 0, h - 1) and
+ *              clamp(j0 + 1, 0, h - 1) of the SOURCE RECTANGLE: nothing bleeds in from the atlas neighbours.  Each tap
+ *              is first turned into rc2dgi_write's value (in RGBA8_COMPAT storage the quantised k * (1/255)); the
+ *              values are lerped in x on both rows, then in y, per channel, with
+ *              lerp(p, q, f) = p + f * (q - p): a difference, a product and a sum.  (Not the fused lerp of the GI
+ *              textures' LINEAR fetch: no GL implementation is matched here, and an unfused lerp is restated exactly
+ *              on a host.)  Like the scaled views of rc2dgi_compose the whole mapping is this library's statement and
+ *              has not been probed against a GL implementation.
+ *   Values     then as for rc2dgi_sprite: src.c = value.c * t.c with the tint t as defined there per storage, the
+ *              blend or RC2DGI_SPRITE_REPLACE exactly as there, the sprites applied in list order on every texel,
+ *              across batches too, and a texel stored only if a sprite or the clear touched it.
+ *   Consequences (POINT):
+ *              A = (w, 0), B = (0, h) and integer px, py leave the bits rc2dgi_sprites_device leaves for
+ *              (sx, sy, w, h, dx = px, dy = py);
+ *              A = (k * w, 0), B = (0, m * h) with whole k, m draws the sub-image with every pixel repeated k x m;
+ *              P = (x + h, y), A = (0, w), B = (-h, 0) is the sub-image turned a quarter clockwise, placed at (x, y);
+ *              P = (x + w, y), A = (-w, 0), B = (0, h) equals the RC2DGI_SPRITE_FLIP_X sprite at (x, y), and
+ *              P = (x + w, y + h), A = (-w, 0), B = (0, -h) equals RC2DGI_SPRITE_FLIP_X | RC2DGI_SPRITE_FLIP_Y.
+ * Errors, each leaving the context valid and the texture untouched: RC2DGI_E_ARG, checked in rc2dgi_sprites_device's
+ * order.  The call only adds an export: RC2DGI_ABI_VERSION stays 5. */
+typedef struct rc2dgi_sprite_xf {
+  int sx, sy, w, h;         /* source rectangle in the atlas, whole pixels, y down (as rc2dgi_sprite) */
+  float px, py;             /* where the source rectangle's top-left CORNER lands, screen pixels, y down */
+  float ax, ay;             /* image of the rectangle's whole top edge (+u over w pixels) */
+  float bx, by;             /* image of the rectangle's whole left edge (+v over h pixels) */
+  unsigned char r, g, b, a; /* tint */
+  unsigned flags;           /* RC2DGI_SPRITE_REPLACE (4) | RC2DGI_SPRITE_LINEAR (8) */
+} rc2dgi_sprite_xf;         /* 48 bytes, twelve 32-bit words */
+enum { RC2DGI_SPRITE_LINEAR = 8 };
+int rc2dgi_sprites_xf_device(rc2dgi_ctx *ctx, int which, const unsigned char *clear_rgba, const rc2dgi_atlas *atlas,
+                             const void *sprites_dev, int n, const void *count_dev, void *status_dev);
+
 /* ---- row-strip sharding of one frame over `world` ranks.
  * rc2dgi_set_shard: the context computes screen rows [rank*H/world, (rank+1)*H/world) of the
  * merged colorRT / tempRT and exactly what they depend on (world = 1: the whole frame again).

@@ -2,7 +2,7 @@
 // timing and the tuning entry points.  The frame itself: rc2dgi_frame.cpp; shards: rc2dgi_group.cpp.
 #include "rc2dgi_ctx.h"
 #include "rc2dgi_read.h"
-#include "rc2dgi_sprites.h"
+#include "rc2dgi_sprites_xf.h"
 
 namespace {
 
@@ -278,36 +278,57 @@ int rc2dgi_paint_device_limits(const rc2dgi_config *cfg, int *batch_prims, long 
   return RC2DGI_OK;
 }
 
-int rc2dgi_sprites_device(rc2dgi_ctx *c, int which, const unsigned char *clear_rgba, const rc2dgi_atlas *atlas,
-                          const void *sprites_dev, int n, const void *count_dev, void *status_dev) {
-  static_assert(sizeof(rc2dgi_sprite) == 32, "a sprite is eight 32-bit words");
+// rc2dgi_sprites_device and rc2dgi_sprites_xf_device: one validation in one order, then `draw` (sprites_device or
+// sprites_xf_device) on the context's working memory and stream
+typedef hipError_t (*SpriteListFn)(float4 *, int, int, int, bool, const unsigned char *, const SpriteAtlas &,
+                                   const void *, int, const void *, void *, PaintDevBuffers &, hipStream_t);
+static int sprite_list_call(rc2dgi_ctx *c, const char *call, SpriteListFn draw, int which,
+                            const unsigned char *clear_rgba, const rc2dgi_atlas *atlas, const void *sprites_dev, int n,
+                            const void *count_dev, void *status_dev) {
   if (!c) return RC2DGI_E_ARG;
   RC2DGI_USABLE(c);
+  const std::string name(call);
   if (which != RC2DGI_RT_COLOR && which != RC2DGI_RT_EMISSIVE)
     return fail(c, RC2DGI_E_ARG, "only COLOR and EMISSIVE are drawn into");
-  if (n < 0 || n > (1 << 20)) return fail(c, RC2DGI_E_ARG, "sprites_device: n is 0 .. 1 << 20");
-  if (!atlas || !atlas->dev) return fail(c, RC2DGI_E_ARG, "sprites_device: null atlas");
+  if (n < 0 || n > (1 << 20)) return fail(c, RC2DGI_E_ARG, name + ": n is 0 .. 1 << 20");
+  if (!atlas || !atlas->dev) return fail(c, RC2DGI_E_ARG, name + ": null atlas");
   if (atlas->w < 1 || atlas->h < 1 || atlas->w > 32768 || atlas->h > 32768)
-    return fail(c, RC2DGI_E_ARG, "sprites_device: the atlas is 1 .. 32768 pixels on each axis");
+    return fail(c, RC2DGI_E_ARG, name + ": the atlas is 1 .. 32768 pixels on each axis");
   if (atlas->format != RC2DGI_FMT_RGBA8 && atlas->format != RC2DGI_FMT_RGBA16F && atlas->format != RC2DGI_FMT_RGBA32F)
-    return fail(c, RC2DGI_E_ARG, "sprites_device: bad atlas format");
+    return fail(c, RC2DGI_E_ARG, name + ": bad atlas format");
   const int pxb = read_pixel_bytes(atlas->format), row = atlas->w * pxb;  // (w <= 32768)
   const int apitch = atlas->pitch_bytes == 0 ? row : atlas->pitch_bytes;
   if (apitch < row || apitch % pxb != 0)
-    return fail(c, RC2DGI_E_ARG, "sprites_device: the atlas pitch is at least a row and a multiple of a pixel");
+    return fail(c, RC2DGI_E_ARG, name + ": the atlas pitch is at least a row and a multiple of a pixel");
   if (reinterpret_cast<uintptr_t>(atlas->dev) % (uintptr_t)pxb != 0)
-    return fail(c, RC2DGI_E_ARG, "sprites_device: the atlas is aligned to a pixel");
-  if (n > 0 && !sprites_dev) return fail(c, RC2DGI_E_ARG, "sprites_device: null sprite list");
+    return fail(c, RC2DGI_E_ARG, name + ": the atlas is aligned to a pixel");
+  if (n > 0 && !sprites_dev) return fail(c, RC2DGI_E_ARG, name + ": null sprite list");
   for (const void *p : {sprites_dev, count_dev, static_cast<const void *>(status_dev)})
     if (reinterpret_cast<uintptr_t>(p) % 4 != 0)
-      return fail(c, RC2DGI_E_ARG, "sprites_device: the list, the count and the status are aligned to 4 bytes");
+      return fail(c, RC2DGI_E_ARG, name + ": the list, the count and the status are aligned to 4 bytes");
   HIPCHK(c, hipSetDevice(c->device));
   float4 *dst = which == RC2DGI_RT_COLOR ? c->color_in : c->emissive;
   const SpriteAtlas a{static_cast<const unsigned char *>(atlas->dev), atlas->w, atlas->h, (size_t)apitch, atlas->format};
-  HIPCHK(c, sprites_device(dst, c->W, c->H, c->sd.pitch, rgba8(c), clear_rgba, a, sprites_dev, n, count_dev, status_dev,
-                           c->paint_dev, c->stream));
+  HIPCHK(c, draw(dst, c->W, c->H, c->sd.pitch, rgba8(c), clear_rgba, a, sprites_dev, n, count_dev, status_dev,
+                 c->paint_dev, c->stream));
   if (which == RC2DGI_RT_COLOR) c->frame_done = false;
   return RC2DGI_OK;
+}
+
+int rc2dgi_sprites_device(rc2dgi_ctx *c, int which, const unsigned char *clear_rgba, const rc2dgi_atlas *atlas,
+                          const void *sprites_dev, int n, const void *count_dev, void *status_dev) {
+  static_assert(sizeof(rc2dgi_sprite) == 32, "a sprite is eight 32-bit words");
+  return sprite_list_call(c, "sprites_device", sprites_device, which, clear_rgba, atlas, sprites_dev, n, count_dev,
+                          status_dev);
+}
+
+int rc2dgi_sprites_xf_device(rc2dgi_ctx *c, int which, const unsigned char *clear_rgba, const rc2dgi_atlas *atlas,
+                             const void *sprites_dev, int n, const void *count_dev, void *status_dev) {
+  static_assert(sizeof(rc2dgi_sprite_xf) == 48 && offsetof(rc2dgi_sprite_xf, px) == 16 &&
+                    offsetof(rc2dgi_sprite_xf, r) == 40 && offsetof(rc2dgi_sprite_xf, flags) == 44,
+                "a transformed sprite is twelve 32-bit words");
+  return sprite_list_call(c, "sprites_xf_device", sprites_xf_device, which, clear_rgba, atlas, sprites_dev, n,
+                          count_dev, status_dev);
 }
 
 int rc2dgi_upload_device(rc2dgi_ctx *c, int which, const void *dev, int pitch_bytes, int format) {

@@ -8,7 +8,8 @@
 //   k_paint_dev_bin   unchanged (paint_dev_enqueue_bin): bit k of the mask of every tile the box meets.
 //   k_sprites_raster  one workgroup a 64 x tile_h tile, a wave a texel row, a lane a texel.  The mask is loaded as
 //                     k_paint_dev_raster loads it; a tile with no bit set and no clear exits before it reads a texel;
-//                     the words found set are zeroed.  The set bits are walked in ascending order, the draw order.  A
+//                     the words found set are zeroed.  The set bits are walked in ascending order, the draw order
+//                     (sprites_walk_tile, rc2dgi_sprites_tile.h, shared with rc2dgi_sprites_xf.hip).  A
 //                     sprite's record is at an address the whole wave shares (scalar loads); the lanes inside its box
 //                     load one atlas pixel each -- a dword, dwordx2 or dwordx4 by the format, adjacent lanes adjacent
 //                     pixels of one atlas row, RC2DGI_SPRITE_FLIP_X only reversing the segment -- and apply
@@ -20,6 +21,7 @@
 
 #include "rc2dgi_device.h"
 #include "rc2dgi_paint_raster.h"
+#include "rc2dgi_sprites_tile.h"
 #include "rc2dgi_write.h"
 
 #include <algorithm>
@@ -90,60 +92,20 @@ __device__ __forceinline__ void sprites_tile(float4 *__restrict__ dst, int W, in
                                              const unsigned char *__restrict__ atlas, size_t apitch) {
   typedef typename WritePixel<FMT>::T P;
   constexpr int PXB = read_pixel_bytes(FMT);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nwords = (mb + 31) >> 5, stride = batch >> 5;
-  unsigned *mask = masks + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * stride;
-  unsigned wd[4];
-  bool any = false;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {  // word q * 64 + lane: below nwords <= stride, so inside the tile's mask
-    const int wi = q * 64 + lane;
-    wd[q] = wi < nwords ? mask[wi] : 0u;
-    any = any || __ballot(wd[q] != 0u) != 0ull;
-  }
-  if (!any && !clear_on) return;  // (every wave loaded the same words: the whole workgroup leaves)
-  if (any) {
-    __syncthreads();  // every wave holds the mask: the words found set go back to zero for the next batch
-    if (wave == 0) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (wd[q] != 0u) mask[q * 64 + lane] = 0u;
-    }
-  }
-  const int i = blockIdx.x * 64 + lane;
-  for (int r = 0; r < tile_h; r += 4) {
-    const int j = blockIdx.y * tile_h + r + wave;
-    if (blockIdx.y * tile_h + r >= H) break;
-    const bool in = i < W && j < H;
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    bool touched = clear_on != 0;
-    if (in) v = clear_on ? make_float4(cr, cg, cb, ca) : dst[(size_t)j * pitch + i];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      unsigned long long nz = __ballot(wd[q] != 0u);
-      while (nz) {
-        const int l = __ffsll((unsigned long long)nz) - 1;
-        nz &= nz - 1;
-        unsigned w = (unsigned)__builtin_amdgcn_readlane((int)wd[q], l);  // (l is the same in every lane)
-        while (w) {
-          const int k = ((q * 64 + l) << 5) + (__ffs(w) - 1);
-          w &= w - 1;
-          const SpriteRec &p = recs[k];  // (k is the same in every lane: one read a wave)
-          if (!in || i < p.x0 || i > p.x1 || j < p.y0 || j > p.y1) continue;
-          // inside the clipped box: (u, v) lies in the source rectangle, which lies in the atlas
-          const int pu = (p.flags & RC2DGI_SPRITE_FLIP_X) ? p.u0 - i : p.u0 + i;
-          const int pv = (p.flags & RC2DGI_SPRITE_FLIP_Y) ? p.v0 + j : p.v0 - j;
-          const P px = *reinterpret_cast<const P *>(atlas + (size_t)pv * apitch + (size_t)pu * PXB);
-          const float4 val = write_value<U8, FMT>(px);
-          const float4 src = make_float4(val.x * p.tint.x, val.y * p.tint.y, val.z * p.tint.z, val.w * p.tint.w);
-          if (p.flags & RC2DGI_SPRITE_REPLACE) v = U8 ? GiU8::unpack(GiU8::pack(src)) : src;
-          else v = U8 ? GiU8::blend(src, v) : blend(src, v);
-          touched = true;
-        }
-      }
-    }
-    if (in && touched) dst[(size_t)j * pitch + i] = v;
-  }
+  sprites_walk_tile(dst, W, H, pitch, clear_on, cr, cg, cb, ca, masks, mb, batch, tile_h,
+                    [&](int k, bool in, int i, int j, float4 &v) {
+    const SpriteRec &p = recs[k];  // (k is the same in every lane: one read a wave)
+    if (!in || i < p.x0 || i > p.x1 || j < p.y0 || j > p.y1) return false;
+    // inside the clipped box: (u, v) lies in the source rectangle, which lies in the atlas
+    const int pu = (p.flags & RC2DGI_SPRITE_FLIP_X) ? p.u0 - i : p.u0 + i;
+    const int pv = (p.flags & RC2DGI_SPRITE_FLIP_Y) ? p.v0 + j : p.v0 - j;
+    const P px = *reinterpret_cast<const P *>(atlas + (size_t)pv * apitch + (size_t)pu * PXB);
+    const float4 val = write_value<U8, FMT>(px);
+    const float4 src = make_float4(val.x * p.tint.x, val.y * p.tint.y, val.z * p.tint.z, val.w * p.tint.w);
+    if (p.flags & RC2DGI_SPRITE_REPLACE) v = U8 ? GiU8::unpack(GiU8::pack(src)) : src;
+    else v = U8 ? GiU8::blend(src, v) : blend(src, v);
+    return true;
+  });
 }
 
 // (the clear colour travels as four floats: a float4 argument is copied to the stack, a store nothing reads)

@@ -70,6 +70,19 @@ class Sprite(ctypes.Structure):
 
 SPRITE_FLIP_X, SPRITE_FLIP_Y, SPRITE_REPLACE = 1, 2, 4
 
+
+class SpriteXf(ctypes.Structure):
+    """rc2dgi_sprite_xf (48 bytes): the source rectangle (sx, sy, w, h) of the atlas mapped onto the parallelogram
+    P, P + A, P + A + B, P + B of the screen (its top-left corner on P = (px, py), its top edge on A = (ax, ay), its
+    left edge on B = (bx, by)), a tint and SPRITE_REPLACE | SPRITE_LINEAR."""
+    _fields_ = [("sx", ctypes.c_int), ("sy", ctypes.c_int), ("w", ctypes.c_int), ("h", ctypes.c_int),
+                ("px", ctypes.c_float), ("py", ctypes.c_float), ("ax", ctypes.c_float), ("ay", ctypes.c_float),
+                ("bx", ctypes.c_float), ("by", ctypes.c_float), ("r", ctypes.c_ubyte), ("g", ctypes.c_ubyte),
+                ("b", ctypes.c_ubyte), ("a", ctypes.c_ubyte), ("flags", ctypes.c_uint)]
+
+
+SPRITE_LINEAR = 8
+
 FILTER_RT, FILTER_POINT, FILTER_LINEAR = 0, 1, 2
 MAX_VIEWS = 16
 RED = (230, 41, 55, 255)  # raylib Color.Red, the thumbnails' border (RC2DGI.cs:435-448)
@@ -302,6 +315,8 @@ def load_library(path: Optional[str] = None):
         "rc2dgi_paint_device_limits": ([ctypes.POINTER(_Config), ip, ctypes.POINTER(ctypes.c_longlong)], ctypes.c_int),
         "rc2dgi_sprites_device": ([vp, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(Atlas), vp,
                                    ctypes.c_int, vp, vp], ctypes.c_int),
+        "rc2dgi_sprites_xf_device": ([vp, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(Atlas), vp,
+                                      ctypes.c_int, vp, vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -513,26 +528,38 @@ class RC2DGI:
         (pack_sprites makes one); clear, count and status as for paint_device.  Each sprite is drawn 1:1 at its integer
         position, tinted, and blended over the texels (SPRITE_REPLACE: replaces them) with write()'s values; a sprite
         the header's rule refuses draws nothing and is counted in status[1].  Keep the tensors alive until sync()."""
+        self._sprite_list("sprites_device", self._L.rc2dgi_sprites_device, 8, which, atlas, sprites, clear, count, status)
+
+    def sprites_xf_device(self, which, atlas, sprites, clear=None, count=None, status=None) -> None:
+        """The same list with every sprite scaled, rotated, sheared or mirrored (rc2dgi_sprites_xf_device): nothing
+        waits.  atlas, clear, count and status as for sprites_device; sprites: a contiguous torch.int32 (n, 12) tensor,
+        a row the twelve words of rc2dgi_sprite_xf (pack_sprites_xf makes one; sprites_xf_from_pro gives its P, A, B
+        from DrawTexturePro's arguments).  Each source rectangle is mapped onto its parallelogram with POINT or, with
+        SPRITE_LINEAR, four-tap sampling inside the rectangle, tinted, and blended over the texels (SPRITE_REPLACE:
+        replaces them); a sprite the header's rule refuses draws nothing and is counted in status[1]."""
+        self._sprite_list("sprites_xf_device", self._L.rc2dgi_sprites_xf_device, 12, which, atlas, sprites, clear, count,
+                          status)
+
+    def _sprite_list(self, call, fn, words, which, atlas, sprites, clear, count, status) -> None:
         w = RT[which] if isinstance(which, str) else int(which)
-        dev_i32 = lambda t, what, numel=None: self._dev_i32("sprites_device", t, what, numel)  # noqa: E731
+        dev_i32 = lambda t, what, numel=None: self._dev_i32(call, t, what, numel)  # noqa: E731
         if not getattr(atlas, "is_cuda", False) or atlas.device.index != self.device:
-            raise TypeError("sprites_device: atlas: expected a tensor on this context's GPU")
+            raise TypeError(f"{call}: atlas: expected a tensor on this context's GPU")
         fmt = _READ_FORMATS.get(str(atlas.dtype).replace("torch.", ""))
         if fmt is None:
-            raise TypeError("sprites_device: atlas: expected a float32, float16 or uint8 tensor")
+            raise TypeError(f"{call}: atlas: expected a float32, float16 or uint8 tensor")
         if atlas.dim() != 3 or atlas.shape[2] != 4 or atlas.stride(2) != 1 or atlas.stride(1) != 4:
-            raise ValueError(f"sprites_device: atlas: expected (AH, AW, 4) with contiguous pixels, got {tuple(atlas.shape)}")
+            raise ValueError(f"{call}: atlas: expected (AH, AW, 4) with contiguous pixels, got {tuple(atlas.shape)}")
         ah, aw = int(atlas.shape[0]), int(atlas.shape[1])
         a = Atlas(atlas.data_ptr(), aw, ah, int(atlas.stride(0)) * atlas.element_size() if ah > 1 else 0, fmt)
         p = dev_i32(sprites, "sprites")
-        if sprites.dim() != 2 or sprites.shape[1] != 8:
-            raise ValueError(f"sprites_device: expected (n, 8) words, got {tuple(sprites.shape)}")
+        if sprites.dim() != 2 or sprites.shape[1] != words:
+            raise ValueError(f"{call}: expected (n, {words}) words, got {tuple(sprites.shape)}")
         n = int(sprites.shape[0])
         cl = None if clear is None else (ctypes.c_ubyte * 4)(*[int(v) for v in clear])
-        self._check(self._L.rc2dgi_sprites_device(self._h, w, cl, ctypes.byref(a), p if n else None, n,
-                                                  None if count is None else dev_i32(count, "count", 1),
-                                                  None if status is None else dev_i32(status, "status", 2)),
-                    f"sprites_device {which}")
+        self._check(fn(self._h, w, cl, ctypes.byref(a), p if n else None, n,
+                       None if count is None else dev_i32(count, "count", 1),
+                       None if status is None else dev_i32(status, "status", 2)), f"{call} {which}")
 
     def download(self, which: str, dtype=np.float32) -> np.ndarray:
         w = RT[which]
@@ -1019,6 +1046,58 @@ def pack_sprites(src_xywh, dst_xy, tint=None, flags=None):
     if tuple(flags.shape) != (n,) or flags.dtype.is_floating_point or flags.dtype == torch.bool:
         raise ValueError(f"pack_sprites: flags is ({n},) of an integer dtype, got {tuple(flags.shape)} {flags.dtype}")
     return torch.cat([src_xywh, dst_xy, tint.contiguous().view(torch.int32), flags.reshape(n, 1).to(torch.int32)], dim=1)
+
+
+def pack_sprites_xf(src_xywh, p_xy, a_xy, b_xy, tint=None, flags=None):
+    """The (n, 12) int32 tensor RC2DGI.sprites_xf_device takes, with torch ops alone on the inputs' device (nothing
+    waits): src_xywh (n, 4) int32, the source rectangles of the atlas; p_xy, a_xy, b_xy (n, 2) float32, where each
+    rectangle's top-left corner lands and the images of its top and left edges (screen pixels, y down); tint (n, 4)
+    uint8, None: white; flags (n,) of any integer dtype (SPRITE_REPLACE | SPRITE_LINEAR), None: 0.  The float bits are
+    reinterpreted; the four tint bytes go little-endian into word 10, as rc2dgi_sprite_xf lays them out."""
+    import torch
+
+    if src_xywh.dim() != 2 or src_xywh.shape[1] != 4 or src_xywh.dtype != torch.int32:
+        raise ValueError(f"pack_sprites_xf: src_xywh is (n, 4) int32, got {tuple(src_xywh.shape)} {src_xywh.dtype}")
+    n = int(src_xywh.shape[0])
+    for name, t in (("p_xy", p_xy), ("a_xy", a_xy), ("b_xy", b_xy)):
+        if tuple(t.shape) != (n, 2) or t.dtype != torch.float32:
+            raise ValueError(f"pack_sprites_xf: {name} is ({n}, 2) float32, got {tuple(t.shape)} {t.dtype}")
+    if tint is None:
+        tint = torch.full((n, 4), 255, dtype=torch.uint8, device=src_xywh.device)
+    if tuple(tint.shape) != (n, 4) or tint.dtype != torch.uint8:
+        raise ValueError(f"pack_sprites_xf: tint is ({n}, 4) uint8, got {tuple(tint.shape)} {tint.dtype}")
+    if flags is None:
+        flags = torch.zeros(n, dtype=torch.int32, device=src_xywh.device)
+    if tuple(flags.shape) != (n,) or flags.dtype.is_floating_point or flags.dtype == torch.bool:
+        raise ValueError(f"pack_sprites_xf: flags is ({n},) of an integer dtype, got {tuple(flags.shape)} {flags.dtype}")
+    return torch.cat([src_xywh, p_xy.contiguous().view(torch.int32), a_xy.contiguous().view(torch.int32),
+                      b_xy.contiguous().view(torch.int32), tint.contiguous().view(torch.int32),
+                      flags.reshape(n, 1).to(torch.int32)], dim=1)
+
+
+def sprites_xf_from_pro(dest_xywh, origin_xy, rotation_deg):
+    """(p_xy, a_xy, b_xy) float32 tensors for pack_sprites_xf from DrawTexturePro's geometry, with torch ops alone:
+    dest_xywh (n, 4) float32, origin_xy (n, 2) float32, rotation_deg (n,) float32 (clockwise on the y-down screen, as
+    raylib turns).  With c, s the cosine and sine of the rotation and R = [[c, -s], [s, c]]:
+    P = dest.xy + R (-origin), A = R (dest.w, 0), B = R (0, dest.h).  The trigonometry is torch's and no part of the
+    exact contract: the device consumes the record as given."""
+    import torch
+
+    n = int(dest_xywh.shape[0])
+    if tuple(dest_xywh.shape) != (n, 4) or dest_xywh.dtype != torch.float32:
+        raise ValueError(f"sprites_xf_from_pro: dest_xywh is (n, 4) float32, got {tuple(dest_xywh.shape)} {dest_xywh.dtype}")
+    if tuple(origin_xy.shape) != (n, 2) or origin_xy.dtype != torch.float32:
+        raise ValueError(f"sprites_xf_from_pro: origin_xy is ({n}, 2) float32, got {tuple(origin_xy.shape)} {origin_xy.dtype}")
+    if tuple(rotation_deg.shape) != (n,) or rotation_deg.dtype != torch.float32:
+        raise ValueError(f"sprites_xf_from_pro: rotation_deg is ({n},) float32, got {tuple(rotation_deg.shape)} "
+                         f"{rotation_deg.dtype}")
+    rad = torch.deg2rad(rotation_deg)
+    c, s = torch.cos(rad), torch.sin(rad)
+    ox, oy = origin_xy[:, 0], origin_xy[:, 1]
+    p = torch.stack([dest_xywh[:, 0] - (c * ox - s * oy), dest_xywh[:, 1] - (s * ox + c * oy)], dim=1)
+    a = torch.stack([c * dest_xywh[:, 2], s * dest_xywh[:, 2]], dim=1)
+    b = torch.stack([-s * dest_xywh[:, 3], c * dest_xywh[:, 3]], dim=1)
+    return p, a, b
 
 
 def paint_device_limits(W: int, H: int):
