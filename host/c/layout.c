@@ -2,7 +2,7 @@
  * tests/test_host_cpu.py to compare with the C# StructLayout(Sequential) mirrors in
  * host/csharp/RC2DGINative.cs (Config, Prim; View: tests/test_present_cpu.py; Ray, RayHit: tests/test_query_cpu.py;
  * Rect, Stats: tests/test_reduce_cpu.py; Tone: tests/test_tone_cpu.py; Atlas, Sprite: tests/test_sprites_cpu.py;
- * SpriteXf: tests/test_sprites_xf_cpu.py). */
+ * SpriteXf: tests/test_sprites_xf_cpu.py; Shape: tests/test_shapes_cpu.py). */
 #include <stddef.h>
 #include <stdio.h>
 
@@ -110,5 +110,12 @@ int main(void) {
   F(rc2dgi_sprite_xf, b);
   F(rc2dgi_sprite_xf, a);
   F(rc2dgi_sprite_xf, flags);
+  printf("rc2dgi_shape %zu\n", sizeof(rc2dgi_shape));
+  F(rc2dgi_shape, kind);
+  F(rc2dgi_shape, v);
+  F(rc2dgi_shape, r);
+  F(rc2dgi_shape, g);
+  F(rc2dgi_shape, b);
+  F(rc2dgi_shape, a);
   return 0;
 }

@@ -98,6 +98,19 @@ static unsafe class RC2DGINative
     public const uint SpriteLinear = 8;
     [DllImport(Lib)] public static extern int rc2dgi_sprites_xf_device(IntPtr ctx, int which, byte* clearRgba, Atlas* atlas, void* spritesDev, int n, void* countDev, void* statusDev);
 
+    // rc2dgi_shapes_device: rectangles, circles, triangles, thick lines and ellipses from a list in device memory,
+    // mixed and painted in list order as rc2dgi_paint_device paints.  V0 .. V5 by Kind: Rect x, y, w, h; Circle x, y,
+    // radius; Triangle x0, y0, x1, y1, x2, y2; Line x0, y0, x1, y1, thick; Ellipse cx, cy, rh, rv.
+    [StructLayout(LayoutKind.Sequential, Size = 32)]
+    public struct Shape
+    {
+        public int Kind;               // ShapeRect .. ShapeEllipse
+        public float V0, V1, V2, V3, V4, V5;
+        public byte R, G, B, A;        // raylib Color
+    }
+    public const int ShapeRect = 0, ShapeCircle = 1, ShapeTriangle = 2, ShapeLine = 3, ShapeEllipse = 4;
+    [DllImport(Lib)] public static extern int rc2dgi_shapes_device(IntPtr ctx, int which, byte* clearRgba, void* shapesDev, int n, void* countDev, void* statusDev);
+
     // rc2dgi_view: one draw of the display frame (window rectangle, y down; Filter 0 = the texture's own,
     // 1 POINT, 2 LINEAR; border A == 0: none)
     [StructLayout(LayoutKind.Sequential)]

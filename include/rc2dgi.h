@@ -872,6 +872,80 @@ enum { RC2DGI_SPRITE_LINEAR = 8 };
 int rc2dgi_sprites_xf_device(rc2dgi_ctx *ctx, int which, const unsigned char *clear_rgba, const rc2dgi_atlas *atlas,
                              const void *sprites_dev, int n, const void *count_dev, void *status_dev);
 
+/* ---- the shapes 2-D level geometry is made of, from a list in device memory: rectangles, circles, triangles, thick
+ * lines and ellipses, mixed in one list and painted in list order.  (Walls kept as a tensor of segments, a triangulated
+ * polygon soup -- raylib's DrawTriangle, DrawLineEx and DrawEllipse beside DrawRectangleRec and DrawCircleV.  A polyline
+ * is its segments as LINEs; the joints are the caller's: a CIRCLE of radius thick / 2 at each.)  Everything not
+ * restated here is word for word rc2dgi_paint_device's: `which`, `clear_rgba`, `count_dev`, `status_dev` ({m, refused})
+ * and m = min(max(*count_dev, 0), n); the error order; the "Order" paragraph (no wait except the first allocation);
+ * the "Memory" paragraph (the same working memory and plan, rc2dgi_paint_device_limits, three kernels a batch, the
+ * "paint_plan" knob honoured); the shards; "painting COLOR makes COLOR the input again"; and the guarantee that a
+ * buffer of garbage paints nothing and faults nothing.
+ *   shapes_dev n records of rc2dgi_shape (32 bytes, eight 32-bit words each) on the context's device, aligned to 4
+ *              bytes; 0 <= n <= 1 << 20.  n == 0 admits a null shapes_dev.
+ *   Arithmetic every float operation named below is one single fp32 operation, rounded to nearest and not fused
+ *              (a * b + c is two roundings); denormals are kept; sqrtf and / are IEEE-correct.  A host that restates
+ *              the rules in float32 gets the device's bits.
+ *   Kinds      v[] by kind; words not named are not read.
+ *     RC2DGI_SHAPE_RECT      v[0..3] = x, y, w, h.
+ *     RC2DGI_SHAPE_CIRCLE    v[0..2] = x, y, radius.
+ *              Both use rc2dgi_prim's refusal test (lim = 2^22, rc2dgi_paint_device's "Refused"), vertex arithmetic
+ *              and triangles, term for term: a list of these two kinds leaves the bits and the `refused` count that
+ *              rc2dgi_paint_device leaves for the same primitives.
+ *     RC2DGI_SHAPE_TRIANGLE  v = x0, y0, x1, y1, x2, y2: one triangle, drawn whatever its winding (the painter makes
+ *              every triangle counter-clockwise; raylib's DrawTriangle asks for counter-clockwise order, and a caller
+ *              who wants that culling orders the vertices itself).
+ *     RC2DGI_SHAPE_LINE      v = x0, y0, x1, y1, thick; v[5] is not read.  The library's statement of raylib 5.5
+ *              DrawLineEx: dx = x1 - x0, dy = y1 - y0, len = sqrtf(dx * dx + dy * dy) (two products, one sum).
+ *              Unless len > 0 && thick > 0 the shape draws nothing and is not refused.  Otherwise
+ *              scale = thick / (2.0f * len), rx = (-scale) * dy, ry = scale * dx, the corners are
+ *              s0 = (x0 - rx, y0 - ry), s1 = (x0 + rx, y0 + ry), s2 = (x1 - rx, y1 - ry), s3 = (x1 + rx, y1 + ry) and the
+ *              triangles {s0, s1, s2} and {s1, s2, s3}.
+ *     RC2DGI_SHAPE_ELLIPSE   v[0..3] = cx, cy, rh, rv.  The library's statement of DrawEllipse:
+ *              T(k) = (cx + c37[k] * rh, cy + s37[k] * rv) with the 37 host cosf / sinf values of DEG2RAD * 10k that
+ *              the circles use, and the 36 triangles (c, T(k + 1), T(k)), k = 0 .. 35.  No radius substitution.
+ *   Refused    a refused shape draws nothing and is counted in `refused`; the other shapes are unaffected.  RECT and
+ *              CIRCLE: as above.  TRIANGLE, LINE, ELLIPSE: every value c the kind reads must pass
+ *              fabsf(c) < 0x1p20f (false for a NaN and for an infinity).  Any other `kind` is refused.
+ *   Ranges     a LINE's |rx|, |ry| stay below 0.62 * 2^20 (|dy| / len <= sqrt(1.5) even where dy * dy is a denormal
+ *              of one bit, and scale stays finite because len >= sqrtf(the least denormal) > 2^-75), so every vertex
+ *              of the three kinds lies below 2^21 pixels.  The window transform keeps x and turns y into H - y with
+ *              H <= 32768, so a snapped coordinate of theirs is below 2^29 + 2^23 in 1/256 pixel.  An edge's a = -dy
+ *              and b = dx are differences of two such numbers, below 2^30 + 2^24: they fit 32 bits.
+ *              c = dy * ax - dx * ay is below 2 * 2^30.1 * 2^29.1 < 2^61, and at a pixel centre (|X|, |Y| < 2^23) the
+ *              raster's 64-bit sum a * X + b * Y + c is below 2^54 + 2^54 + 2^61 < 2^63.  RECT and CIRCLE keep
+ *              rc2dgi_paint's bound and arithmetic.  The binning evaluates the same sums at pixel centres of the
+ *              target only, as the raster does.
+ *   Vertices to pixels  as rc2dgi_paint: the window transform, the snap to 1/256 pixel, dropping zero-area triangles,
+ *              the counter-clockwise swap, the rule for centres exactly on an edge, the clipped pixel box.  A shape
+ *              covers a texel when one of its triangles does; it blends over that texel ONCE, in list order, across
+ *              batches too.  A shape wholly off the target draws nothing and is not refused.  Like the sprites, the
+ *              vertex lists of the three new kinds have not been probed against a GL implementation; the coverage
+ *              rule they feed has (the circles' fans, arbitrary slopes).
+ *   Binning    a shape is tested only in the 64 x tile_h tiles in which one of its triangles can cover a pixel centre
+ *              (an exact test on the integer edge equations); a thin diagonal LINE costs the tiles under it, not the
+ *              tiles of its box.  The test only skips tiles in which no centre is covered: it changes no result.
+ *   Consequences
+ *              a TRIANGLE leaves the same bits for all six orders of its vertices;
+ *              the TRIANGLEs (x,y),(x,y+h),(x+w,y+h) and (x,y),(x+w,y+h),(x+w,y) together leave RECT (x, y, w, h)'s
+ *              bits for whole-number x, y, w, h, for a translucent colour too: a centre on the shared diagonal belongs
+ *              to exactly one of them;
+ *              LINE (4, y) -> (36, y) with thick 6 leaves RECT (4, y - 3, 32, 6)'s bits, and so for any length that
+ *              is a power of two with whole coordinates;
+ *              ELLIPSE with rh == rv == r > 0 leaves CIRCLE (cx, cy, r)'s bits;
+ *              an ELLIPSE with a zero radius draws nothing.
+ * Errors, each leaving the context valid and the texture untouched: RC2DGI_E_ARG, checked in rc2dgi_paint_device's
+ * order.  The call only adds an export: RC2DGI_ABI_VERSION stays 5. */
+typedef struct rc2dgi_shape {
+  int kind;                  /* RC2DGI_SHAPE_* */
+  float v[6];                /* by kind, above */
+  unsigned char r, g, b, a;  /* raylib Color */
+} rc2dgi_shape;              /* 32 bytes, eight 32-bit words */
+enum { RC2DGI_SHAPE_RECT = 0, RC2DGI_SHAPE_CIRCLE = 1, RC2DGI_SHAPE_TRIANGLE = 2, RC2DGI_SHAPE_LINE = 3,
+       RC2DGI_SHAPE_ELLIPSE = 4 };
+int rc2dgi_shapes_device(rc2dgi_ctx *ctx, int which, const unsigned char *clear_rgba, const void *shapes_dev, int n,
+                         const void *count_dev, void *status_dev);
+
 /* ---- row-strip sharding of one frame over `world` ranks.
  * rc2dgi_set_shard: the context computes screen rows [rank*H/world, (rank+1)*H/world) of the
  * merged colorRT / tempRT and exactly what they depend on (world = 1: the whole frame again).

@@ -2,6 +2,7 @@
 // timing and the tuning entry points.  The frame itself: rc2dgi_frame.cpp; shards: rc2dgi_group.cpp.
 #include "rc2dgi_ctx.h"
 #include "rc2dgi_read.h"
+#include "rc2dgi_shapes.h"
 #include "rc2dgi_sprites_xf.h"
 
 namespace {
@@ -249,23 +250,45 @@ int rc2dgi_paint(rc2dgi_ctx *c, int which, const unsigned char *clear_rgba, cons
   return RC2DGI_OK;
 }
 
-int rc2dgi_paint_device(rc2dgi_ctx *c, int which, const unsigned char *clear_rgba, const void *prims_dev, int n,
-                        const void *count_dev, void *status_dev) {
+// rc2dgi_paint_device and rc2dgi_shapes_device: one validation in one order, then `draw` (paint_prims_device or
+// shapes_device) on the context's working memory and stream.  Rec is the list's record: its size is checked where the
+// call is named.
+typedef hipError_t (*PaintListFn)(float4 *, int, int, int, bool, const unsigned char *, const void *, int, const void *,
+                                  void *, PaintDevBuffers &, hipStream_t);
+extern "C++" template <class Rec, size_t Bytes>
+static int paint_list_call(rc2dgi_ctx *c, const char *call, PaintListFn draw, int which,
+                           const unsigned char *clear_rgba, const void *list_dev, int n, const void *count_dev,
+                           void *status_dev) {
+  static_assert(sizeof(Rec) == Bytes && Bytes % 4 == 0, "a record of the list is whole 32-bit words");
   if (!c) return RC2DGI_E_ARG;
   RC2DGI_USABLE(c);
+  const std::string name(call);
   if (which != RC2DGI_RT_COLOR && which != RC2DGI_RT_EMISSIVE)
     return fail(c, RC2DGI_E_ARG, "only COLOR and EMISSIVE are painted");
-  if (n < 0 || n > (1 << 20)) return fail(c, RC2DGI_E_ARG, "paint_device: n is 0 .. 1 << 20");
-  if (n > 0 && !prims_dev) return fail(c, RC2DGI_E_ARG, "paint_device: null primitive list");
-  for (const void *p : {prims_dev, count_dev, static_cast<const void *>(status_dev)})
+  if (n < 0 || n > (1 << 20)) return fail(c, RC2DGI_E_ARG, name + ": n is 0 .. 1 << 20");
+  if (n > 0 && !list_dev) return fail(c, RC2DGI_E_ARG, name + ": null primitive list");
+  for (const void *p : {list_dev, count_dev, static_cast<const void *>(status_dev)})
     if (reinterpret_cast<uintptr_t>(p) % 4 != 0)
-      return fail(c, RC2DGI_E_ARG, "paint_device: the list, the count and the status are aligned to 4 bytes");
+      return fail(c, RC2DGI_E_ARG, name + ": the list, the count and the status are aligned to 4 bytes");
   HIPCHK(c, hipSetDevice(c->device));
   float4 *dst = which == RC2DGI_RT_COLOR ? c->color_in : c->emissive;
-  HIPCHK(c, paint_prims_device(dst, c->W, c->H, c->sd.pitch, rgba8(c), clear_rgba, prims_dev, n, count_dev, status_dev,
-                               c->paint_dev, c->stream));
+  HIPCHK(c, draw(dst, c->W, c->H, c->sd.pitch, rgba8(c), clear_rgba, list_dev, n, count_dev, status_dev, c->paint_dev,
+                 c->stream));
   if (which == RC2DGI_RT_COLOR) c->frame_done = false;
   return RC2DGI_OK;
+}
+
+int rc2dgi_paint_device(rc2dgi_ctx *c, int which, const unsigned char *clear_rgba, const void *prims_dev, int n,
+                        const void *count_dev, void *status_dev) {
+  return paint_list_call<rc2dgi_prim, 24>(c, "paint_device", paint_prims_device, which, clear_rgba, prims_dev, n,
+                                          count_dev, status_dev);
+}
+
+int rc2dgi_shapes_device(rc2dgi_ctx *c, int which, const unsigned char *clear_rgba, const void *shapes_dev, int n,
+                         const void *count_dev, void *status_dev) {
+  static_assert(offsetof(rc2dgi_shape, v) == 4 && offsetof(rc2dgi_shape, r) == 28, "a shape is eight 32-bit words");
+  return paint_list_call<rc2dgi_shape, 32>(c, "shapes_device", shapes_device, which, clear_rgba, shapes_dev, n,
+                                           count_dev, status_dev);
 }
 
 int rc2dgi_paint_device_limits(const rc2dgi_config *cfg, int *batch_prims, long long *work_bytes) {

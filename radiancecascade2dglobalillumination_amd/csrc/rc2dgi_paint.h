@@ -68,6 +68,12 @@ float4 paint_dev_clear(const unsigned char *clear, bool u8);
 // PaintPrim does -- the clipped pixel box in words 0 .. 3, word 5 (ntri) positive when the record draws.
 void paint_dev_enqueue_bin(const void *recs, int n, const int *count_dev, int base, int nb, const PaintDevPlan &plan,
                            unsigned *masks, hipStream_t st);
+// k_paint_dev_raster over every tile of the plan, for the batch at `base`: prims / tris are the batch's PaintPrim and
+// PaintTri records (rc2dgi_paint_raster.h), clear_on applies `clear` first (the first batch of a call with a clear).
+// rc2dgi_shapes_device (rc2dgi_shapes.hip) runs it unchanged on records of its own set-up.
+void paint_dev_enqueue_raster(float4 *dst, int W, int H, int pitch, bool u8, bool clear_on, float4 clear,
+                              const void *prims, const void *tris, unsigned *masks, int n, const int *count_dev,
+                              int base, const PaintDevPlan &plan, hipStream_t st);
 // k_paint_dev_finish: {m, refused} to `status` (null: nothing) and the refusal counter, counters[0], back to zero.
 void paint_dev_enqueue_finish(unsigned *counters, const int *count_dev, int n, int *status, hipStream_t st);
 

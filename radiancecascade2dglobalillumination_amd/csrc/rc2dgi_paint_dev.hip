@@ -20,6 +20,7 @@
 #include "rc2dgi_paint.h"
 #include "rc2dgi_device.h"
 #include "rc2dgi_paint_raster.h"
+#include "rc2dgi_paint_setup.h"
 
 #include <algorithm>
 #include <climits>
@@ -27,64 +28,6 @@
 namespace rc2dgi {
 
 namespace {
-
-constexpr int kPaintDevHead = 256;        // bytes of counters ahead of the records: word 0 counts refused primitives
-constexpr int kPaintDevTris = 36;         // triangle slots a primitive (a circle's 18 quads)
-
-struct PaintCircle {
-  float c[37], s[37];
-};
-
-struct PaintXform {  // to_window's constants, computed on the host as to_window computes them
-  float sx, sy, hw, hh;
-  int W, H;
-};
-
-struct PaintSnap {
-  long long x, y;
-};
-
-__device__ __forceinline__ PaintSnap paint_dev_window(float vx, float vy, const PaintXform &t) {
-  const float xn = __fadd_rn(__fmul_rn(vx, t.sx), -1.0f);
-  const float yn = __fadd_rn(__fmul_rn(vy, t.sy), 1.0f);
-  const float xw = __fadd_rn(__fmul_rn(xn, t.hw), t.hw), yw = __fadd_rn(__fmul_rn(yn, t.hh), t.hh);
-  return PaintSnap{(long long)rint((double)xw * 256.0), (long long)rint((double)yw * 256.0)};
-}
-
-__device__ __forceinline__ long long paint_dev_floor_div(long long a, long long b) {
-  return a >= 0 ? a / b : -((-a + b - 1) / b);
-}
-
-struct PaintAcc {
-  PaintTri *out;
-  int nt;
-  long long mnx, mny, mxx, mxy;
-};
-
-// one triangle of paint_prims' loop: dropped when its area is zero, made counter-clockwise, its three edges
-__device__ __forceinline__ void paint_dev_emit(PaintAcc &A, PaintSnap s0, PaintSnap s1, PaintSnap s2) {
-  const long long area = (s1.x - s0.x) * (s2.y - s0.y) - (s2.x - s0.x) * (s1.y - s0.y);
-  if (area == 0) return;
-  if (area < 0) {
-    const PaintSnap t = s1;
-    s1 = s2;
-    s2 = t;
-  }
-  const PaintSnap s[3] = {s0, s1, s2};
-  PaintTri tri{};
-#pragma unroll
-  for (int e = 0; e < 3; ++e) {
-    const PaintSnap a = s[e], b = s[(e + 1) % 3];
-    const long long dx = b.x - a.x, dy = b.y - a.y;
-    tri.e[e].a = (int)(-dy);
-    tri.e[e].b = (int)dx;
-    tri.e[e].c = dy * a.x - dx * a.y;
-    if (dy < 0 || (dy == 0 && dx > 0)) tri.incl |= 1u << e;
-    A.mnx = min(A.mnx, a.x); A.mxx = max(A.mxx, a.x);
-    A.mny = min(A.mny, a.y); A.mxy = max(A.mxy, a.y);
-  }
-  A.out[A.nt++] = tri;
-}
 
 __global__ __launch_bounds__(256) void k_paint_dev_setup(const unsigned *__restrict__ list, int n,
                                                          const int *__restrict__ count_dev, int base, int batch,
@@ -274,6 +217,14 @@ void paint_dev_enqueue_bin(const void *recs, int n, const int *count_dev, int ba
                      count_dev, base, plan.batch, masks, plan.tiles_x, th_shift);
 }
 
+void paint_dev_enqueue_raster(float4 *dst, int W, int H, int pitch, bool u8, bool clear_on, float4 clear,
+                              const void *prims, const void *tris, unsigned *masks, int n, const int *count_dev,
+                              int base, const PaintDevPlan &plan, hipStream_t st) {
+  hipLaunchKernelGGL(k_paint_dev_raster, dim3(plan.tiles_x, plan.tiles_y), dim3(256), 0, st, dst, W, H, pitch,
+                     clear_on ? 1 : 0, clear, static_cast<const PaintPrim *>(prims),
+                     static_cast<const PaintTri *>(tris), masks, n, count_dev, base, plan.batch, plan.tile_h, (int)u8);
+}
+
 void paint_dev_enqueue_finish(unsigned *counters, const int *count_dev, int n, int *status, hipStream_t st) {
   hipLaunchKernelGGL(k_paint_dev_finish, dim3(1), dim3(1), 0, st, counters, count_dev, n, status);
 }
@@ -314,9 +265,7 @@ hipError_t paint_prims_device(float4 *dst, int W, int H, int pitch, bool u8, con
                          tab);
       paint_dev_enqueue_bin(prims, n, cnt, base, nb, plan, masks, st);
     }
-    hipLaunchKernelGGL(k_paint_dev_raster, dim3(plan.tiles_x, plan.tiles_y), dim3(256), 0, st, dst, W, H, pitch,
-                       clear && b == 0 ? 1 : 0, cl, static_cast<const PaintPrim *>(prims),
-                       static_cast<const PaintTri *>(tris), masks, n, cnt, base, plan.batch, plan.tile_h, (int)u8);
+    paint_dev_enqueue_raster(dst, W, H, pitch, u8, clear && b == 0, cl, prims, tris, masks, n, cnt, base, plan, st);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

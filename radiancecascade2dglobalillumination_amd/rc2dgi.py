@@ -83,6 +83,16 @@ class SpriteXf(ctypes.Structure):
 
 SPRITE_LINEAR = 8
 
+
+class Shape(ctypes.Structure):
+    """rc2dgi_shape (32 bytes): kind SHAPE_*, six floats by kind (RECT x, y, w, h; CIRCLE x, y, radius; TRIANGLE
+    x0, y0, x1, y1, x2, y2; LINE x0, y0, x1, y1, thick; ELLIPSE cx, cy, rh, rv) and a raylib Color."""
+    _fields_ = [("kind", ctypes.c_int), ("v", ctypes.c_float * 6), ("r", ctypes.c_ubyte), ("g", ctypes.c_ubyte),
+                ("b", ctypes.c_ubyte), ("a", ctypes.c_ubyte)]
+
+
+SHAPE_RECT, SHAPE_CIRCLE, SHAPE_TRIANGLE, SHAPE_LINE, SHAPE_ELLIPSE = 0, 1, 2, 3, 4
+
 FILTER_RT, FILTER_POINT, FILTER_LINEAR = 0, 1, 2
 MAX_VIEWS = 16
 RED = (230, 41, 55, 255)  # raylib Color.Red, the thumbnails' border (RC2DGI.cs:435-448)
@@ -312,6 +322,8 @@ def load_library(path: Optional[str] = None):
         "rc2dgi_write_device": ([vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int], ctypes.c_int),
         "rc2dgi_paint_device": ([vp, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), vp, ctypes.c_int, vp, vp],
                                 ctypes.c_int),
+        "rc2dgi_shapes_device": ([vp, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), vp, ctypes.c_int, vp, vp],
+                                 ctypes.c_int),
         "rc2dgi_paint_device_limits": ([ctypes.POINTER(_Config), ip, ctypes.POINTER(ctypes.c_longlong)], ctypes.c_int),
         "rc2dgi_sprites_device": ([vp, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(Atlas), vp,
                                    ctypes.c_int, vp, vp], ctypes.c_int),
@@ -508,17 +520,26 @@ class RC2DGI:
         of two elements that receives {painted, refused}.  A primitive paint() would raise on draws nothing and is
         counted in `refused`.  Keep the tensors alive until sync(); they may be overwritten on the same stream as soon
         as the call has returned."""
+        self._paint_list("paint_device", self._L.rc2dgi_paint_device, 6, "prims", which, prims, clear, count, status)
+
+    def shapes_device(self, which, shapes, clear=None, count=None, status=None) -> None:
+        """Rectangles, circles, triangles, thick lines and ellipses from a list in device memory, mixed and painted
+        in list order (rc2dgi_shapes_device): nothing waits.  shapes: a contiguous torch.int32 (n, 8) tensor on this
+        context's GPU, a row the eight words of rc2dgi_shape (pack_shapes makes one, shapes_from_prims turns a
+        paint_device list into one); clear, count and status as for paint_device.  A shape the header's rule refuses
+        draws nothing and is counted in status[1].  Keep the tensors alive until sync()."""
+        self._paint_list("shapes_device", self._L.rc2dgi_shapes_device, 8, "shapes", which, shapes, clear, count, status)
+
+    def _paint_list(self, call, fn, words, what, which, recs, clear, count, status) -> None:
         w = RT[which] if isinstance(which, str) else int(which)
-        dev_i32 = lambda t, what, numel=None: self._dev_i32("paint_device", t, what, numel)  # noqa: E731
-        p = dev_i32(prims, "prims")
-        if prims.dim() != 2 or prims.shape[1] != 6:
-            raise ValueError(f"paint_device: expected (n, 6) words, got {tuple(prims.shape)}")
-        n = int(prims.shape[0])
+        dev_i32 = lambda t, what, numel=None: self._dev_i32(call, t, what, numel)  # noqa: E731
+        p = dev_i32(recs, what)
+        if recs.dim() != 2 or recs.shape[1] != words:
+            raise ValueError(f"{call}: expected (n, {words}) words, got {tuple(recs.shape)}")
+        n = int(recs.shape[0])
         cl = None if clear is None else (ctypes.c_ubyte * 4)(*[int(v) for v in clear])
-        self._check(self._L.rc2dgi_paint_device(self._h, w, cl, p if n else None, n,
-                                                None if count is None else dev_i32(count, "count", 1),
-                                                None if status is None else dev_i32(status, "status", 2)),
-                    f"paint_device {which}")
+        self._check(fn(self._h, w, cl, p if n else None, n, None if count is None else dev_i32(count, "count", 1),
+                       None if status is None else dev_i32(status, "status", 2)), f"{call} {which}")
 
     def sprites_device(self, which, atlas, sprites, clear=None, count=None, status=None) -> None:
         """A sprite list in device memory drawn from one atlas image, enqueued on the context stream
@@ -1023,6 +1044,35 @@ def pack_prims(kind, xywh, rgba):
         raise ValueError(f"pack_prims: rgba is ({n}, 4) uint8, got {tuple(rgba.shape)} {rgba.dtype}")
     return torch.cat([kind.reshape(n, 1).to(torch.int32), xywh.contiguous().view(torch.int32),
                       rgba.contiguous().view(torch.int32)], dim=1)
+
+
+def pack_shapes(kind, v6, rgba):
+    """The (n, 8) int32 tensor RC2DGI.shapes_device takes, with torch ops alone on the inputs' device (nothing waits):
+    kind (n,) of any integer dtype (SHAPE_*), v6 (n, 6) float32 (the values the kind names; the rest are not read),
+    rgba (n, 4) uint8.  The float bits are reinterpreted; the four colour bytes go little-endian into word 7, as
+    rc2dgi_shape lays them out."""
+    import torch
+
+    n = int(kind.shape[0])
+    if tuple(kind.shape) != (n,) or kind.dtype.is_floating_point or kind.dtype == torch.bool:
+        raise ValueError(f"pack_shapes: kind is (n,) of an integer dtype, got {tuple(kind.shape)} {kind.dtype}")
+    if tuple(v6.shape) != (n, 6) or v6.dtype != torch.float32:
+        raise ValueError(f"pack_shapes: v6 is ({n}, 6) float32, got {tuple(v6.shape)} {v6.dtype}")
+    if tuple(rgba.shape) != (n, 4) or rgba.dtype != torch.uint8:
+        raise ValueError(f"pack_shapes: rgba is ({n}, 4) uint8, got {tuple(rgba.shape)} {rgba.dtype}")
+    return torch.cat([kind.reshape(n, 1).to(torch.int32), v6.contiguous().view(torch.int32),
+                      rgba.contiguous().view(torch.int32)], dim=1)
+
+
+def shapes_from_prims(prims):
+    """The (n, 8) shapes_device list that paints what the (n, 6) paint_device list `prims` paints: kind, x, y, w, h
+    in words 0 .. 4, two zero words, the colour in word 7 (SHAPE_RECT == 0 and SHAPE_CIRCLE == 1 are rc2dgi_prim's
+    kinds).  Torch ops alone on the input's device."""
+    import torch
+
+    if prims.dim() != 2 or prims.shape[1] != 6 or prims.dtype != torch.int32:
+        raise ValueError(f"shapes_from_prims: prims is (n, 6) int32, got {tuple(prims.shape)} {prims.dtype}")
+    return torch.cat([prims[:, :5], torch.zeros_like(prims[:, :2]), prims[:, 5:6]], dim=1).contiguous()
 
 
 def pack_sprites(src_xywh, dst_xy, tint=None, flags=None):
