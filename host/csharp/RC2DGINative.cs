@@ -111,6 +111,27 @@ static unsafe class RC2DGINative
     public const int ShapeRect = 0, ShapeCircle = 1, ShapeTriangle = 2, ShapeLine = 3, ShapeEllipse = 4;
     [DllImport(Lib)] public static extern int rc2dgi_shapes_device(IntPtr ctx, int which, byte* clearRgba, void* shapesDev, int n, void* countDev, void* statusDev);
 
+    // rc2dgi_tilemap_device: a tile map drawn as one layer -- a Rows x Cols grid of 32-bit cell words in device memory
+    // (Tiled's global tile ids: 0 an empty cell, bit 31 / 30 the horizontal / vertical flip), cells of TileW x TileH
+    // pixels from a tile set (the atlas) of SetCols tiles a row with Tiled's Margin and Spacing, cell (0, 0) at (Ox, Oy)
+    // of the screen: scrolling is those two integers.  No list and no working memory; statusDev: null or two int32
+    // that receive {drawn, refused} over the visible cells.  Flags: SpriteReplace or 0.
+    [StructLayout(LayoutKind.Sequential, Size = 56)]
+    public struct Tilemap
+    {
+        public void* CellsDev;         // Rows x Cols words on the context's device, row 0 the top row
+        public int Cols, Rows;         // 0 .. 32768
+        public int PitchCells;         // 0 = Cols
+        public int TileW, TileH;       // 1 .. 32768
+        public int Ox, Oy;             // the scroll, within 2^22 of zero
+        public int SetCols;            // 1 .. 32768
+        public int Margin, Spacing;    // 0 .. 32768
+        public byte R, G, B, A;        // tint of the whole layer
+        public uint Flags;             // SpriteReplace or 0
+    }
+    public const uint TileFlipX = 0x80000000, TileFlipY = 0x40000000;
+    [DllImport(Lib)] public static extern int rc2dgi_tilemap_device(IntPtr ctx, int which, byte* clearRgba, Atlas* atlas, Tilemap* map, void* statusDev);
+
     // rc2dgi_view: one draw of the display frame (window rectangle, y down; Filter 0 = the texture's own,
     // 1 POINT, 2 LINEAR; border A == 0: none)
     [StructLayout(LayoutKind.Sequential)]

@@ -946,6 +946,74 @@ enum { RC2DGI_SHAPE_RECT = 0, RC2DGI_SHAPE_CIRCLE = 1, RC2DGI_SHAPE_TRIANGLE = 2
 int rc2dgi_shapes_device(rc2dgi_ctx *ctx, int which, const unsigned char *clear_rgba, const void *shapes_dev, int n,
                          const void *count_dev, void *status_dev);
 
+/* ---- a tile map: a regular grid of cell words in device memory, each an index into a tile set (an atlas image), drawn
+ * as one layer.  (What most 2-D levels are made of: the layers Tiled and LDtk write and every raylib tile-map loader
+ * draws with one DrawTextureRec a cell.)  A grid needs none of the list machinery: a pixel's cell is a division of its
+ * own coordinates and cells never overlap, so there is no draw order, no batch, no working memory; scrolling is the
+ * two integers ox, oy.  `which`, `clear_rgba` and `atlas` are rc2dgi_sprites_device's; `map` is a host struct, read
+ * during the call.
+ *   The grid   cells_dev is rows x cols 32-bit cell words on the context's device, aligned to 4 bytes, row 0 the TOP
+ *              row, the word of cell (c, r) at cells_dev[r * pitch + c] with pitch = pitch_cells, or cols where
+ *              pitch_cells == 0 (a window of a larger world is a pointer to its first cell and the world's pitch).
+ *              cols and rows are 0 .. 32768; an empty grid (cols * rows == 0) admits a null cells_dev.  Cell (c, r)
+ *              covers the screen pixels dx <= X < dx + tile_w, dy <= Y < dy + tile_h with dx = ox + c * tile_w and
+ *              dy = oy + r * tile_h (raylib screen coordinates, y down), clipped to the W x H target.
+ *   Cell word  Tiled's global tile id as it is: a Tiled layer uploaded as uint32 needs no conversion.  g == 0 is an
+ *              empty cell: it draws nothing and is not refused.  Otherwise id = g & 0x0FFFFFFF, t = id - 1,
+ *              tx = t % set_cols, ty = t / set_cols; bit 31 flips the tile horizontally and bit 30 vertically
+ *              (RC2DGI_SPRITE_FLIP_X / _FLIP_Y of the tile); bits 29 (diagonal) and 28 (hexagonal) are not supported.
+ *              The tile's rectangle of the atlas is sx = margin + tx * (tile_w + spacing),
+ *              sy = margin + ty * (tile_h + spacing), tile_w x tile_h pixels (Tiled's margin and spacing).
+ *   Refused    the device cannot fail a call, so a refused cell draws nothing and is counted; the other cells are
+ *              unaffected.  With AW x AH the atlas size, max_tx = (AW - margin - tile_w) / (tile_w + spacing) and
+ *              max_ty = (AH - margin - tile_h) / (tile_h + spacing) (computed once on the host, in this form, so
+ *              nothing overflows), a non-empty cell is refused when
+ *                bit 29 or bit 28 of g is set, or
+ *                id == 0 (a word of flag bits alone), or
+ *                tx > max_tx or ty > max_ty: the tile's rectangle would not lie in the atlas.
+ *   Pixels and values   cell (c, r) is the sprite {sx, sy, tile_w, tile_h, dx, dy, the tint r, g, b, a,
+ *              flip bits | (flags & RC2DGI_SPRITE_REPLACE)} of rc2dgi_sprites_device, whose "Pixels" and "Values"
+ *              paragraphs apply unchanged: 1:1, POINT, rc2dgi_write's value of the atlas pixel, one multiply a channel
+ *              by the tint, and the blend or the replacement in the context's storage.  So after the call the texture
+ *              holds the bits rc2dgi_sprites_device leaves for the list of the non-empty, accepted cells that meet
+ *              the target, in any order, with the same clear.  (Every such cell has -tile_w < dx < W and
+ *              -tile_h < dy < H, so dx and dy are always admissible there.)  With a clear colour every texel that no
+ *              such cell covers becomes the clear's value; without one it keeps its bits.
+ *   Status     status_dev is NULL or two int32 on the device, aligned to 4 bytes, that receive {drawn, refused} on the
+ *              stream on every call.  Both count the VISIBLE cells only, those with at least one pixel inside the
+ *              target (a 32768 x 32768 world is not walked for a 1200 x 900 window): `drawn` the visible non-empty
+ *              accepted cells, `refused` the visible refused cells.  The sums are integer and independent of order.
+ *              With NULL nothing is counted.
+ *   Garbage    nothing read from cells_dev becomes an address or an index before the refusal test: the cell index comes
+ *              from the pixel's own coordinates, clipped to the grid, the atlas index from a tile the test found inside
+ *              the atlas.  A grid of random words draws what the rule accepts and faults nothing.
+ *   Order      as rc2dgi_sprites_device: the call is enqueued behind whatever is in flight on the context stream and
+ *              returns without waiting (the first call with a status allocates the context's counters, 8 KiB, the one
+ *              exception; the painters' working memory is not touched).  Without a clear the work covers only the
+ *              map's pixel box clipped to the target; a map scrolled off the target costs nothing and still writes
+ *              {0, 0} to a non-null status.  The grid, the atlas and the status stay alive until rc2dgi_sync(); the
+ *              grid and the atlas must not overlap the context's textures.  Drawing into COLOR makes COLOR the input
+ *              again.  Row-strip shards accept the call: the inputs are replicated whole on every rank.
+ * Errors, each leaving the context valid and the texture untouched: RC2DGI_E_ARG, checked in this order, for a null
+ * context, a bad `which`, a null atlas or atlas->dev or a bad atlas size, format, pitch or alignment (the checks and the
+ * messages of rc2dgi_sprites_device), a null map, flags & ~4, cols or rows out of range, pitch_cells neither 0 nor in
+ * cols .. 1 << 20, tile_w or tile_h out of range, ox or oy outside [-2^22, 2^22], set_cols, margin or spacing out of
+ * range, margin + tile_w > AW or margin + tile_h > AH (tile 0 does not fit), a null cells_dev with cols * rows > 0,
+ * cells_dev or status_dev not aligned to 4 bytes.  The call only adds an export: RC2DGI_ABI_VERSION stays 5. */
+typedef struct rc2dgi_tilemap {
+  const void *cells_dev;    /* rows x cols 32-bit cell words on the context's device, aligned to 4 bytes, row 0 the TOP row */
+  int cols, rows;           /* 0 .. 32768 each; an empty grid admits a null cells_dev */
+  int pitch_cells;          /* words from one cell row to the next; 0 = cols; otherwise cols .. 1 << 20 */
+  int tile_w, tile_h;       /* 1 .. 32768: a cell's size on the screen and a tile's size in the atlas, pixels */
+  int ox, oy;               /* screen position (raylib, y down) of the top-left pixel of cell (0, 0); |.| <= 2^22: the scroll */
+  int set_cols;             /* tiles per row of the tile set, 1 .. 32768 */
+  int margin, spacing;      /* Tiled's: pixels around the set and between tiles, 0 .. 32768 each */
+  unsigned char r, g, b, a; /* tint of the whole layer */
+  unsigned flags;           /* RC2DGI_SPRITE_REPLACE (4) or 0 */
+} rc2dgi_tilemap;           /* 56 bytes */
+int rc2dgi_tilemap_device(rc2dgi_ctx *ctx, int which, const unsigned char *clear_rgba, const rc2dgi_atlas *atlas,
+                          const rc2dgi_tilemap *map, void *status_dev);
+
 /* ---- row-strip sharding of one frame over `world` ranks.
  * rc2dgi_set_shard: the context computes screen rows [rank*H/world, (rank+1)*H/world) of the
  * merged colorRT / tempRT and exactly what they depend on (world = 1: the whole frame again).

@@ -79,6 +79,8 @@ void free_buffers(rc2dgi_ctx *c) {
   c->rc_maps.clear();
   c->paint_buf.release();
   c->paint_dev.release();
+  if (c->tilemap_cnt) (void)hipFree(c->tilemap_cnt);
+  c->tilemap_cnt = nullptr;
   if (c->present_buf) (void)hipFree(c->present_buf);
   c->present_buf = nullptr;
   c->present_cap = 0;

@@ -4,6 +4,7 @@
 #include "rc2dgi_read.h"
 #include "rc2dgi_shapes.h"
 #include "rc2dgi_sprites_xf.h"
+#include "rc2dgi_tilemap.h"
 
 namespace {
 
@@ -301,6 +302,24 @@ int rc2dgi_paint_device_limits(const rc2dgi_config *cfg, int *batch_prims, long 
   return RC2DGI_OK;
 }
 
+// The atlas checks of the sprite calls and rc2dgi_tilemap_device, in one order and one wording; `a` is the atlas
+// with its pitch resolved.
+static int atlas_check(rc2dgi_ctx *c, const std::string &name, const rc2dgi_atlas *atlas, SpriteAtlas &a) {
+  if (!atlas || !atlas->dev) return fail(c, RC2DGI_E_ARG, name + ": null atlas");
+  if (atlas->w < 1 || atlas->h < 1 || atlas->w > 32768 || atlas->h > 32768)
+    return fail(c, RC2DGI_E_ARG, name + ": the atlas is 1 .. 32768 pixels on each axis");
+  if (atlas->format != RC2DGI_FMT_RGBA8 && atlas->format != RC2DGI_FMT_RGBA16F && atlas->format != RC2DGI_FMT_RGBA32F)
+    return fail(c, RC2DGI_E_ARG, name + ": bad atlas format");
+  const int pxb = read_pixel_bytes(atlas->format), row = atlas->w * pxb;  // (w <= 32768)
+  const int apitch = atlas->pitch_bytes == 0 ? row : atlas->pitch_bytes;
+  if (apitch < row || apitch % pxb != 0)
+    return fail(c, RC2DGI_E_ARG, name + ": the atlas pitch is at least a row and a multiple of a pixel");
+  if (reinterpret_cast<uintptr_t>(atlas->dev) % (uintptr_t)pxb != 0)
+    return fail(c, RC2DGI_E_ARG, name + ": the atlas is aligned to a pixel");
+  a = SpriteAtlas{static_cast<const unsigned char *>(atlas->dev), atlas->w, atlas->h, (size_t)apitch, atlas->format};
+  return RC2DGI_OK;
+}
+
 // rc2dgi_sprites_device and rc2dgi_sprites_xf_device: one validation in one order, then `draw` (sprites_device or
 // sprites_xf_device) on the context's working memory and stream
 typedef hipError_t (*SpriteListFn)(float4 *, int, int, int, bool, const unsigned char *, const SpriteAtlas &,
@@ -314,24 +333,14 @@ static int sprite_list_call(rc2dgi_ctx *c, const char *call, SpriteListFn draw, 
   if (which != RC2DGI_RT_COLOR && which != RC2DGI_RT_EMISSIVE)
     return fail(c, RC2DGI_E_ARG, "only COLOR and EMISSIVE are drawn into");
   if (n < 0 || n > (1 << 20)) return fail(c, RC2DGI_E_ARG, name + ": n is 0 .. 1 << 20");
-  if (!atlas || !atlas->dev) return fail(c, RC2DGI_E_ARG, name + ": null atlas");
-  if (atlas->w < 1 || atlas->h < 1 || atlas->w > 32768 || atlas->h > 32768)
-    return fail(c, RC2DGI_E_ARG, name + ": the atlas is 1 .. 32768 pixels on each axis");
-  if (atlas->format != RC2DGI_FMT_RGBA8 && atlas->format != RC2DGI_FMT_RGBA16F && atlas->format != RC2DGI_FMT_RGBA32F)
-    return fail(c, RC2DGI_E_ARG, name + ": bad atlas format");
-  const int pxb = read_pixel_bytes(atlas->format), row = atlas->w * pxb;  // (w <= 32768)
-  const int apitch = atlas->pitch_bytes == 0 ? row : atlas->pitch_bytes;
-  if (apitch < row || apitch % pxb != 0)
-    return fail(c, RC2DGI_E_ARG, name + ": the atlas pitch is at least a row and a multiple of a pixel");
-  if (reinterpret_cast<uintptr_t>(atlas->dev) % (uintptr_t)pxb != 0)
-    return fail(c, RC2DGI_E_ARG, name + ": the atlas is aligned to a pixel");
+  SpriteAtlas a{};
+  if (const int rc = atlas_check(c, name, atlas, a)) return rc;
   if (n > 0 && !sprites_dev) return fail(c, RC2DGI_E_ARG, name + ": null sprite list");
   for (const void *p : {sprites_dev, count_dev, static_cast<const void *>(status_dev)})
     if (reinterpret_cast<uintptr_t>(p) % 4 != 0)
       return fail(c, RC2DGI_E_ARG, name + ": the list, the count and the status are aligned to 4 bytes");
   HIPCHK(c, hipSetDevice(c->device));
   float4 *dst = which == RC2DGI_RT_COLOR ? c->color_in : c->emissive;
-  const SpriteAtlas a{static_cast<const unsigned char *>(atlas->dev), atlas->w, atlas->h, (size_t)apitch, atlas->format};
   HIPCHK(c, draw(dst, c->W, c->H, c->sd.pitch, rgba8(c), clear_rgba, a, sprites_dev, n, count_dev, status_dev,
                  c->paint_dev, c->stream));
   if (which == RC2DGI_RT_COLOR) c->frame_done = false;
@@ -352,6 +361,53 @@ int rc2dgi_sprites_xf_device(rc2dgi_ctx *c, int which, const unsigned char *clea
                 "a transformed sprite is twelve 32-bit words");
   return sprite_list_call(c, "sprites_xf_device", sprites_xf_device, which, clear_rgba, atlas, sprites_dev, n,
                           count_dev, status_dev);
+}
+
+int rc2dgi_tilemap_device(rc2dgi_ctx *c, int which, const unsigned char *clear_rgba, const rc2dgi_atlas *atlas,
+                          const rc2dgi_tilemap *map, void *status_dev) {
+  static_assert(sizeof(rc2dgi_tilemap) == 56 && offsetof(rc2dgi_tilemap, cols) == 8 &&
+                    offsetof(rc2dgi_tilemap, r) == 48 && offsetof(rc2dgi_tilemap, flags) == 52,
+                "a tile map is a pointer, ten ints, a tint and the flags");
+  if (!c) return RC2DGI_E_ARG;
+  RC2DGI_USABLE(c);
+  const std::string name("tilemap_device");
+  if (which != RC2DGI_RT_COLOR && which != RC2DGI_RT_EMISSIVE)
+    return fail(c, RC2DGI_E_ARG, "only COLOR and EMISSIVE are drawn into");
+  SpriteAtlas a{};
+  if (const int rc = atlas_check(c, name, atlas, a)) return rc;
+  if (!map) return fail(c, RC2DGI_E_ARG, name + ": null map");
+  const rc2dgi_tilemap &m = *map;
+  auto in = [](int v, int lo, int hi) { return v >= lo && v <= hi; };
+  if (m.flags & ~(unsigned)RC2DGI_SPRITE_REPLACE) return fail(c, RC2DGI_E_ARG, name + ": flags is RC2DGI_SPRITE_REPLACE or 0");
+  if (!in(m.cols, 0, 32768) || !in(m.rows, 0, 32768)) return fail(c, RC2DGI_E_ARG, name + ": cols and rows are 0 .. 32768");
+  if (m.pitch_cells != 0 && !in(m.pitch_cells, m.cols, 1 << 20))
+    return fail(c, RC2DGI_E_ARG, name + ": pitch_cells is 0 or cols .. 1 << 20");
+  if (!in(m.tile_w, 1, 32768) || !in(m.tile_h, 1, 32768))
+    return fail(c, RC2DGI_E_ARG, name + ": tile_w and tile_h are 1 .. 32768");
+  if (!in(m.ox, -(1 << 22), 1 << 22) || !in(m.oy, -(1 << 22), 1 << 22))
+    return fail(c, RC2DGI_E_ARG, name + ": ox and oy are within 2^22 of zero");
+  if (!in(m.set_cols, 1, 32768) || !in(m.margin, 0, 32768) || !in(m.spacing, 0, 32768))
+    return fail(c, RC2DGI_E_ARG, name + ": set_cols is 1 .. 32768, margin and spacing are 0 .. 32768");
+  if (m.margin + m.tile_w > a.w || m.margin + m.tile_h > a.h)
+    return fail(c, RC2DGI_E_ARG, name + ": tile 0 does not fit the atlas");
+  if (!m.cells_dev && (long long)m.cols * m.rows > 0) return fail(c, RC2DGI_E_ARG, name + ": null cells");
+  for (const void *p : {m.cells_dev, static_cast<const void *>(status_dev)})
+    if (reinterpret_cast<uintptr_t>(p) % 4 != 0)
+      return fail(c, RC2DGI_E_ARG, name + ": the cells and the status are aligned to 4 bytes");
+  TilemapLayer layer{};
+  layer.cells = static_cast<const unsigned *>(m.cells_dev);
+  layer.g = TilemapGeom{m.cols, m.rows, m.pitch_cells == 0 ? std::max(m.cols, 1) : m.pitch_cells, m.tile_w, m.tile_h,
+                        m.ox, m.oy, m.set_cols, m.margin, m.tile_w + m.spacing, m.tile_h + m.spacing,
+                        tilemap_max_tile(a.w, m.margin, m.tile_w, m.spacing),
+                        tilemap_max_tile(a.h, m.margin, m.tile_h, m.spacing)};
+  layer.tint[0] = m.r, layer.tint[1] = m.g, layer.tint[2] = m.b, layer.tint[3] = m.a;
+  layer.replace = (m.flags & RC2DGI_SPRITE_REPLACE) != 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  float4 *dst = which == RC2DGI_RT_COLOR ? c->color_in : c->emissive;
+  HIPCHK(c, tilemap_device(dst, c->W, c->H, c->sd.pitch, rgba8(c), clear_rgba, a, layer, status_dev, &c->tilemap_cnt,
+                           c->stream));
+  if (which == RC2DGI_RT_COLOR) c->frame_done = false;
+  return RC2DGI_OK;
 }
 
 int rc2dgi_upload_device(rc2dgi_ctx *c, int which, const void *dev, int pitch_bytes, int format) {

@@ -93,6 +93,20 @@ class Shape(ctypes.Structure):
 
 SHAPE_RECT, SHAPE_CIRCLE, SHAPE_TRIANGLE, SHAPE_LINE, SHAPE_ELLIPSE = 0, 1, 2, 3, 4
 
+
+class Tilemap(ctypes.Structure):
+    """rc2dgi_tilemap (56 bytes): a rows x cols grid of 32-bit cell words on the device (Tiled's global tile ids, 0 an
+    empty cell, bit 31 / 30 the horizontal / vertical flip), cells of tile_w x tile_h pixels with cell (0, 0) at (ox, oy)
+    of the screen, the tile set's layout (set_cols, margin, spacing), the layer's tint and SPRITE_REPLACE or 0."""
+    _fields_ = [("cells_dev", ctypes.c_void_p), ("cols", ctypes.c_int), ("rows", ctypes.c_int),
+                ("pitch_cells", ctypes.c_int), ("tile_w", ctypes.c_int), ("tile_h", ctypes.c_int), ("ox", ctypes.c_int),
+                ("oy", ctypes.c_int), ("set_cols", ctypes.c_int), ("margin", ctypes.c_int), ("spacing", ctypes.c_int),
+                ("r", ctypes.c_ubyte), ("g", ctypes.c_ubyte), ("b", ctypes.c_ubyte), ("a", ctypes.c_ubyte),
+                ("flags", ctypes.c_uint)]
+
+
+TILE_FLIP_X, TILE_FLIP_Y, TILE_UNSUPPORTED, TILE_ID_MASK = 0x80000000, 0x40000000, 0x30000000, 0x0FFFFFFF
+
 FILTER_RT, FILTER_POINT, FILTER_LINEAR = 0, 1, 2
 MAX_VIEWS = 16
 RED = (230, 41, 55, 255)  # raylib Color.Red, the thumbnails' border (RC2DGI.cs:435-448)
@@ -329,6 +343,8 @@ def load_library(path: Optional[str] = None):
                                    ctypes.c_int, vp, vp], ctypes.c_int),
         "rc2dgi_sprites_xf_device": ([vp, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(Atlas), vp,
                                       ctypes.c_int, vp, vp], ctypes.c_int),
+        "rc2dgi_tilemap_device": ([vp, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(Atlas),
+                                   ctypes.POINTER(Tilemap), vp], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -561,9 +577,8 @@ class RC2DGI:
         self._sprite_list("sprites_xf_device", self._L.rc2dgi_sprites_xf_device, 12, which, atlas, sprites, clear, count,
                           status)
 
-    def _sprite_list(self, call, fn, words, which, atlas, sprites, clear, count, status) -> None:
-        w = RT[which] if isinstance(which, str) else int(which)
-        dev_i32 = lambda t, what, numel=None: self._dev_i32(call, t, what, numel)  # noqa: E731
+    def _atlas(self, call, atlas):
+        """the rc2dgi_atlas of an (AH, AW, 4) tensor on this context's GPU (the sprite calls and tilemap_device)"""
         if not getattr(atlas, "is_cuda", False) or atlas.device.index != self.device:
             raise TypeError(f"{call}: atlas: expected a tensor on this context's GPU")
         fmt = _READ_FORMATS.get(str(atlas.dtype).replace("torch.", ""))
@@ -572,7 +587,12 @@ class RC2DGI:
         if atlas.dim() != 3 or atlas.shape[2] != 4 or atlas.stride(2) != 1 or atlas.stride(1) != 4:
             raise ValueError(f"{call}: atlas: expected (AH, AW, 4) with contiguous pixels, got {tuple(atlas.shape)}")
         ah, aw = int(atlas.shape[0]), int(atlas.shape[1])
-        a = Atlas(atlas.data_ptr(), aw, ah, int(atlas.stride(0)) * atlas.element_size() if ah > 1 else 0, fmt)
+        return Atlas(atlas.data_ptr(), aw, ah, int(atlas.stride(0)) * atlas.element_size() if ah > 1 else 0, fmt)
+
+    def _sprite_list(self, call, fn, words, which, atlas, sprites, clear, count, status) -> None:
+        w = RT[which] if isinstance(which, str) else int(which)
+        dev_i32 = lambda t, what, numel=None: self._dev_i32(call, t, what, numel)  # noqa: E731
+        a = self._atlas(call, atlas)
         p = dev_i32(sprites, "sprites")
         if sprites.dim() != 2 or sprites.shape[1] != words:
             raise ValueError(f"{call}: expected (n, {words}) words, got {tuple(sprites.shape)}")
@@ -581,6 +601,42 @@ class RC2DGI:
         self._check(fn(self._h, w, cl, ctypes.byref(a), p if n else None, n,
                        None if count is None else dev_i32(count, "count", 1),
                        None if status is None else dev_i32(status, "status", 2)), f"{call} {which}")
+
+    def tilemap_device(self, which, atlas, cells, tile, origin=(0, 0), set_cols=None, margin=0, spacing=0, tint=None,
+                       replace=False, clear=None, status=None) -> None:
+        """A tile map drawn as one layer, enqueued on the context stream (rc2dgi_tilemap_device): nothing waits.
+        atlas: the tile set, as for sprites_device; cells: a (rows, cols) torch.int32 tensor on this context's GPU with
+        stride(1) == 1, row 0 the top row (its row stride is the pitch, so a window of a larger world tensor is
+        accepted), a word Tiled's global tile id: 0 an empty cell, bit 31 / 30 (TILE_FLIP_X / TILE_FLIP_Y) the flips;
+        tile: (tile_w, tile_h); origin: where the top-left pixel of cell (0, 0) goes (the scroll); set_cols: tiles per
+        row of the set, None: Tiled's (AW - 2 * margin + spacing) // (tile_w + spacing); tint: (r, g, b, a) of the
+        whole layer, None: white; replace: SPRITE_REPLACE; clear as for paint_device; status: None or an int32 tensor of
+        two elements that receives {drawn, refused} over the visible cells.  A cell the header's rule refuses draws
+        nothing.  Layers that need a tint a cell go through tilemap_sprites and sprites_device.  Keep the tensors alive
+        until sync()."""
+        call = "tilemap_device"
+        w = RT[which] if isinstance(which, str) else int(which)
+        a = self._atlas(call, atlas)
+        if not getattr(cells, "is_cuda", False) or cells.device.index != self.device:
+            raise TypeError(f"{call}: cells: expected a tensor on this context's GPU")
+        if str(cells.dtype) != "torch.int32":
+            raise TypeError(f"{call}: cells: expected an int32 tensor")
+        if cells.dim() != 2 or (cells.shape[1] > 1 and cells.stride(1) != 1):
+            raise ValueError(f"{call}: cells: expected (rows, cols) with contiguous rows, got {tuple(cells.shape)}")
+        rows, cols = int(cells.shape[0]), int(cells.shape[1])
+        if rows > 1 and cells.stride(0) < cols:
+            raise ValueError(f"{call}: cells: the row stride {cells.stride(0)} is smaller than a row of {cols} cells")
+        tw, th = (int(v) for v in tile)
+        if set_cols is None:
+            set_cols = tilemap_set_cols(a.w, tw, margin, spacing)
+        r, g, b, al = (255, 255, 255, 255) if tint is None else (int(v) for v in tint)
+        m = Tilemap(cells.data_ptr() if rows * cols else None, cols, rows, int(cells.stride(0)) if rows > 1 else 0, tw,
+                    th, int(origin[0]), int(origin[1]), int(set_cols), int(margin), int(spacing), r, g, b, al,
+                    SPRITE_REPLACE if replace else 0)
+        cl = None if clear is None else (ctypes.c_ubyte * 4)(*[int(v) for v in clear])
+        self._check(self._L.rc2dgi_tilemap_device(self._h, w, cl, ctypes.byref(a), ctypes.byref(m),
+                                                  None if status is None else self._dev_i32(call, status, "status", 2)),
+                    f"{call} {which}")
 
     def download(self, which: str, dtype=np.float32) -> np.ndarray:
         w = RT[which]
@@ -1096,6 +1152,53 @@ def pack_sprites(src_xywh, dst_xy, tint=None, flags=None):
     if tuple(flags.shape) != (n,) or flags.dtype.is_floating_point or flags.dtype == torch.bool:
         raise ValueError(f"pack_sprites: flags is ({n},) of an integer dtype, got {tuple(flags.shape)} {flags.dtype}")
     return torch.cat([src_xywh, dst_xy, tint.contiguous().view(torch.int32), flags.reshape(n, 1).to(torch.int32)], dim=1)
+
+
+def tilemap_set_cols(atlas_w: int, tile_w: int, margin: int = 0, spacing: int = 0) -> int:
+    """Tiled's column count of a tile set image: (AW - 2 * margin + spacing) // (tile_w + spacing)"""
+    return (int(atlas_w) - 2 * int(margin) + int(spacing)) // (int(tile_w) + int(spacing))
+
+
+def tilemap_sprites(cells, tile, origin, atlas_size, screen_size, set_cols=None, margin=0, spacing=0, tint=None,
+                    replace=False):
+    """The (n, 8) int32 sprite list (pack_sprites' layout) of the cells RC2DGI.tilemap_device draws: the visible,
+    non-empty, accepted cells of `cells` ((rows, cols) int32, on any device) in row-major order, with torch ops alone on
+    that device.  tile = (tile_w, tile_h), origin = (ox, oy), atlas_size = (AW, AH), screen_size = (W, H); the other
+    arguments as for tilemap_device.  sprites_device on the list leaves the bits tilemap_device leaves: the fallback for
+    layers that need a tint a cell (overwrite column 6) or, through sprites_xf_device, a zoomed camera."""
+    import torch
+
+    if cells.dim() != 2 or cells.dtype != torch.int32:
+        raise ValueError(f"tilemap_sprites: cells is (rows, cols) int32, got {tuple(cells.shape)} {cells.dtype}")
+    (tw, th), (ox, oy), (AW, AH), (W, H) = ((int(v[0]), int(v[1])) for v in (tile, origin, atlas_size, screen_size))
+    margin, spacing = int(margin), int(spacing)
+    if tw < 1 or th < 1 or margin < 0 or spacing < 0 or margin + tw > AW or margin + th > AH:
+        raise ValueError("tilemap_sprites: tile 0 does not fit the atlas")
+    set_cols = tilemap_set_cols(AW, tw, margin, spacing) if set_cols is None else int(set_cols)
+    if set_cols < 1:
+        raise ValueError(f"tilemap_sprites: set_cols is at least 1, got {set_cols}")
+    rows, cols = int(cells.shape[0]), int(cells.shape[1])
+    # the visible cells: ox + c * tw + tw - 1 >= 0 and ox + c * tw <= W - 1 (floor divisions), and rows alike
+    c0, c1 = max(-ox // tw, 0), min((W - 1 - ox) // tw, cols - 1)
+    r0, r1 = max(-oy // th, 0), min((H - 1 - oy) // th, rows - 1)
+    if c0 > c1 or r0 > r1:
+        return torch.zeros((0, 8), dtype=torch.int32, device=cells.device)
+    g = cells[r0:r1 + 1, c0:c1 + 1].to(torch.int64) & 0xFFFFFFFF
+    t = (g & TILE_ID_MASK) - 1
+    tx, ty = t % set_cols, t // set_cols
+    ok = (g != 0) & ((g & TILE_UNSUPPORTED) == 0) & (t >= 0)
+    ok &= (tx <= (AW - margin - tw) // (tw + spacing)) & (ty <= (AH - margin - th) // (th + spacing))
+    r, c = torch.nonzero(ok, as_tuple=True)  # row-major
+    g, tx, ty = g[r, c], tx[r, c], ty[r, c]
+    n = int(r.numel())
+    flags = ((g >> 31) & 1) * SPRITE_FLIP_X + ((g >> 30) & 1) * SPRITE_FLIP_Y + (SPRITE_REPLACE if replace else 0)
+    rgba = (255, 255, 255, 255) if tint is None else tuple(int(v) & 255 for v in tint)
+    word = rgba[0] | rgba[1] << 8 | rgba[2] << 16 | rgba[3] << 24
+    word -= (1 << 32) if word >= (1 << 31) else 0
+    out = torch.stack([margin + tx * (tw + spacing), margin + ty * (th + spacing), torch.full_like(tx, tw),
+                       torch.full_like(tx, th), ox + (c + c0) * tw, oy + (r + r0) * th, torch.full_like(tx, word),
+                       flags], dim=1)
+    return out.to(torch.int32).reshape(n, 8)
 
 
 def pack_sprites_xf(src_xywh, p_xy, a_xy, b_xy, tint=None, flags=None):
