@@ -2,7 +2,8 @@
  * tests/test_host_cpu.py to compare with the C# StructLayout(Sequential) mirrors in
  * host/csharp/RC2DGINative.cs (Config, Prim; View: tests/test_present_cpu.py; Ray, RayHit: tests/test_query_cpu.py;
  * Rect, Stats: tests/test_reduce_cpu.py; Tone: tests/test_tone_cpu.py; Atlas, Sprite: tests/test_sprites_cpu.py;
- * SpriteXf: tests/test_sprites_xf_cpu.py; Shape: tests/test_shapes_cpu.py). */
+ * SpriteXf: tests/test_sprites_xf_cpu.py; Shape: tests/test_shapes_cpu.py;
+ * Gradient: tests/test_gradients_cpu.py). */
 #include <stddef.h>
 #include <stdio.h>
 
@@ -117,5 +118,10 @@ int main(void) {
   F(rc2dgi_shape, g);
   F(rc2dgi_shape, b);
   F(rc2dgi_shape, a);
+  printf("rc2dgi_gradient %zu\n", sizeof(rc2dgi_gradient));
+  F(rc2dgi_gradient, kind);
+  F(rc2dgi_gradient, v);
+  F(rc2dgi_gradient, c);
+  F(rc2dgi_gradient, gain);
   return 0;
 }

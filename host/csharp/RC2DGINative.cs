@@ -111,6 +111,22 @@ static unsafe class RC2DGINative
     public const int ShapeRect = 0, ShapeCircle = 1, ShapeTriangle = 2, ShapeLine = 3, ShapeEllipse = 4;
     [DllImport(Lib)] public static extern int rc2dgi_shapes_device(IntPtr ctx, int which, byte* clearRgba, void* shapesDev, int n, void* countDev, void* statusDev);
 
+    // rc2dgi_gradients_device: the same five shapes with a colour a vertex and an HDR gain (soft round lights, beams,
+    // washed walls).  V0 .. V5 by Kind as Shape's.  Colours by Kind: Triangle C0 .. C2, one a vertex; Rect C0 .. C3 =
+    // TL, BL, BR, TR; Circle and Ellipse C0 the centre, C1 the rim; Line C0 the (x0, y0) end, C1 the other.  Each is
+    // a raylib Color packed r | g << 8 | b << 16 | a << 24 (its bytes in memory order).  Gain multiplies r, g, b
+    // after the interpolation.
+    [StructLayout(LayoutKind.Sequential, Size = 48)]
+    public struct Gradient
+    {
+        public int Kind;               // GradRect .. GradEllipse
+        public float V0, V1, V2, V3, V4, V5;
+        public uint C0, C1, C2, C3;    // raylib Colors, bytes r, g, b, a
+        public float Gain;
+    }
+    public const int GradRect = 0, GradCircle = 1, GradTriangle = 2, GradLine = 3, GradEllipse = 4;
+    [DllImport(Lib)] public static extern int rc2dgi_gradients_device(IntPtr ctx, int which, byte* clearRgba, void* gradsDev, int n, void* countDev, void* statusDev);
+
     // rc2dgi_tilemap_device: a tile map drawn as one layer -- a Rows x Cols grid of 32-bit cell words in device memory
     // (Tiled's global tile ids: 0 an empty cell, bit 31 / 30 the horizontal / vertical flip), cells of TileW x TileH
     // pixels from a tile set (the atlas) of SetCols tiles a row with Tiled's Margin and Spacing, cell (0, 0) at (Ox, Oy)

@@ -946,6 +946,89 @@ enum { RC2DGI_SHAPE_RECT = 0, RC2DGI_SHAPE_CIRCLE = 1, RC2DGI_SHAPE_TRIANGLE = 2
 int rc2dgi_shapes_device(rc2dgi_ctx *ctx, int which, const unsigned char *clear_rgba, const void *shapes_dev, int n,
                          const void *count_dev, void *status_dev);
 
+/* ---- the same five shapes with a colour a vertex and an HDR gain, from a list in device memory: what a 2-D scene is
+ * lit with.  (A soft round light, bright at the centre and fading to nothing at the rim -- raylib's DrawCircleGradient;
+ * a beam that fades along its length; a wall washed from one colour into another -- DrawRectangleGradientEx / H / V; a
+ * triangle with a colour at each vertex.  A particle system kept as a tensor and used as lights.)  Everything not
+ * restated here is word for word rc2dgi_shapes_device's, and through it rc2dgi_paint_device's: `which`, `clear_rgba`,
+ * `count_dev`, `status_dev` ({m, refused}) and m = min(max(*count_dev, 0), n); the error order; the "Order" paragraph
+ * (no wait except the first allocation); the "Memory" paragraph (the same working memory and plan,
+ * rc2dgi_paint_device_limits, three kernels a batch, the "paint_plan" knob honoured; the call owns no memory of its
+ * own); the "Binning" paragraph; the shards; "painting COLOR makes COLOR the input again"; and the guarantee that a
+ * buffer of garbage paints nothing and faults nothing (colour bytes and the gain never become an address).
+ *   grads_dev  n records of rc2dgi_gradient (48 bytes, twelve 32-bit words each) on the context's device, aligned to 4
+ *              bytes; 0 <= n <= 1 << 20.  n == 0 admits a null grads_dev.  The records are read by the set-up of their
+ *              batch alone.
+ *   Arithmetic every float operation named below is one single fp32 operation, rounded to nearest and not fused;
+ *              denormals are kept and / is IEEE-correct.  (float)E of a 64-bit integer E is one round-to-nearest-even
+ *              conversion.  A host that restates the rules in float32 and int64 gets the device's bits.
+ *   Geometry   v[] by kind is rc2dgi_shape's v[] of the kind of the same name, and so are the kind's vertex list and
+ *              triangles, term for term.  The triangles, in the order in which they are LISTED, vertices in listed order:
+ *     RC2DGI_GRAD_RECT      (TL, BL, BR), then (TL, BR, TR).
+ *     RC2DGI_GRAD_CIRCLE    (centre, T(k + 1), T(k)), k = 0 .. 35, with the radius substitution.
+ *     RC2DGI_GRAD_ELLIPSE   (centre, T(k + 1), T(k)), k = 0 .. 35, without it.
+ *     RC2DGI_GRAD_TRIANGLE  its three vertices as given.
+ *     RC2DGI_GRAD_LINE      {s0, s1, s2}, then {s1, s2, s3}.
+ *              The window transform, the snap to 1/256 pixel, the zero-area drop, the counter-clockwise swap, the
+ *              `incl` rule for centres exactly on an edge, the clipped pixel box and the exact tile rejection are
+ *              rc2dgi_paint's and rc2dgi_shapes_device's.
+ *   Colours by kind   c[k] is a raylib Color, bytes r, g, b, a; bytes not named are not read.
+ *     TRIANGLE         c[0..2], one per vertex in order.
+ *     RECT             c[0..3] = TL, BL, BR, TR.  This corner order is the library's statement of a two-triangle
+ *              gradient quad; the argument order of raylib's DrawRectangleGradientEx differs between raylib versions
+ *              (INTEGRATION.md gives the mapping from its argument names).
+ *     CIRCLE, ELLIPSE  c[0] at the centre, c[1] at every rim vertex T(k).
+ *     LINE             c[0] at s0 and s1 (the (x0, y0) end), c[1] at s2 and s3.
+ *              A colour byte k becomes (float)k * (1.0f / 255.0f) in every storage mode (rc2dgi_shapes_device's
+ *              conversion).
+ *   Which triangle   a texel centre may be covered by more than one triangle of a shape (at a radius near 2^20 the
+ *              fan's T(36) and T(0) differ by a fraction of a pixel).  The FIRST covering triangle in the listed order
+ *              supplies the colour; dropped triangles are skipped.
+ *   Interpolation   let the covering triangle's vertices in listed order be R0, R1, R2 with colours q0, q1, q2.  At the
+ *              centre (X, Y) = (256 i + 128, 256 j + 128), E_k is the 64-bit edge function of the edge joining the
+ *              other two vertices, oriented so that the inside is positive (the same number whether or not the
+ *              triangle was swapped), and A = E_0 + E_1 + E_2 is twice the triangle's area, the same at every centre.
+ *              rc2dgi_shapes_device's "Ranges" make each |E| smaller than 2^61 + 2^55, so the sum stays below 2^63
+ *              (for RECT and CIRCLE, with rc2dgi_paint's bound: at a covered centre no E is negative and they sum to
+ *              twice the area, below 2^62).  Then
+ *                w1 = (float)E_1 / (float)A,  w2 = (float)E_2 / (float)A,
+ *                col = (q0 + w1 * (q1 - q0)) + w2 * (q2 - q0)   per channel, alpha included: two differences, two
+ *                                                               products, two sums, in that order,
+ *                src.rgb = col.rgb * gain (one multiply each),  src.a = col.a.
+ *   Values     src is treated exactly as rc2dgi_write treats an RGBA32F pixel of that value with RC2DGI_WRITE_BLEND:
+ *              in F32 and F16 storage the texel becomes src.c * a + texel.c * (1 - a) with a = src.a; in RGBA8_COMPAT
+ *              storage the 8-bit blend of q8(src) over the texel (q8 clamps first, so the gain saturates at 255
+ *              there).  A shape blends over a texel ONCE, in list order, across batches too.
+ *   Refused    a refused record draws nothing and is counted in `refused`; the others are unaffected.  The geometry test
+ *              is that of the rc2dgi_shape kind of the same name (RECT and CIRCLE: rc2dgi_prim's at 2^22; the others:
+ *              fabsf(c) < 0x1p20f for every value read).  In addition a record whose gain fails
+ *              fabsf(gain) <= 0x1p20f is refused (false for a NaN and for an infinity; a negative gain is accepted).
+ *              Any other `kind` is refused.
+ *   Consequences
+ *              a record whose named colours are all equal and whose gain is 1.0f leaves the bits and the `refused`
+ *              count rc2dgi_shapes_device leaves for the shape of the same kind, v[] and colour, in all three storage
+ *              modes (every difference q1 - q0 is exactly 0, and q8(k * (1/255)) is k for all 256 values of k);
+ *              a centre exactly on an included edge has weight exactly 0 for the opposite vertex;
+ *              a CIRCLE with c[1] = {r, g, b, 0} contributes nothing at a centre that lies on the rim edge of its
+ *              triangle: there E_0 = 0, so w1 + w2 is 1 but for three roundings each, |col.a| stays below 2^-21, and
+ *              in RGBA8_COMPAT storage q8 makes it 0 and the texel keeps its bits; where c[0].a is 0 too, col.a is
+ *              exactly 0 and the texel keeps its value in every storage mode.
+ *              Like the vertex lists of the three new shape kinds, the interpolation is this library's statement: it
+ *              has not been probed against a GL implementation (a GL rasteriser interpolates with plane equations of
+ *              its own precision).
+ * Errors, each leaving the context valid and the texture untouched: RC2DGI_E_ARG, checked in rc2dgi_paint_device's
+ * order.  The call only adds an export and a struct: RC2DGI_ABI_VERSION stays 5. */
+typedef struct rc2dgi_gradient {
+  int kind;                 /* RC2DGI_GRAD_* */
+  float v[6];               /* geometry by kind, exactly rc2dgi_shape's v[] for the kind of the same name */
+  unsigned char c[4][4];    /* up to four raylib Colors (r, g, b, a), by kind */
+  float gain;               /* multiplies r, g, b (not alpha) after interpolation: HDR lights */
+} rc2dgi_gradient;          /* 48 bytes, twelve 32-bit words */
+enum { RC2DGI_GRAD_RECT = 0, RC2DGI_GRAD_CIRCLE = 1, RC2DGI_GRAD_TRIANGLE = 2, RC2DGI_GRAD_LINE = 3,
+       RC2DGI_GRAD_ELLIPSE = 4 };
+int rc2dgi_gradients_device(rc2dgi_ctx *ctx, int which, const unsigned char *clear_rgba, const void *grads_dev, int n,
+                            const void *count_dev, void *status_dev);
+
 /* ---- a tile map: a regular grid of cell words in device memory, each an index into a tile set (an atlas image), drawn
  * as one layer.  (What most 2-D levels are made of: the layers Tiled and LDtk write and every raylib tile-map loader
  * draws with one DrawTextureRec a cell.)  A grid needs none of the list machinery: a pixel's cell is a division of its

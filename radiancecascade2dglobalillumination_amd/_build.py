@@ -19,13 +19,14 @@ SOURCES = ["rc2dgi_jfa.hip", "rc2dgi_side.hip", "rc2dgi_blur.hip", "rc2dgi_copy.
            "rc2dgi_present.hip", "rc2dgi_query.hip", "rc2dgi_reduce.hip", "rc2dgi_tone.hip", "rc2dgi_hist.hip",
            "rc2dgi_read.hip", "rc2dgi_rectplan.cpp", "rc2dgi_display.cpp", "rc2dgi_regions.cpp", "rc2dgi_points.cpp",
            "rc2dgi_write.hip", "rc2dgi_paint_dev.hip", "rc2dgi_sprites.hip", "rc2dgi_sprites_xf.hip", "rc2dgi_shapes.hip",
-           "rc2dgi_tilemap.hip"]
+           "rc2dgi_tilemap.hip", "rc2dgi_gradients.hip"]
 HEADERS = ["rc2dgi_device.h", "rc2dgi_kernels.h", "rc2dgi_launch.h", "rc2dgi_rc.h", "rc2dgi_shard.h", "rc2dgi_paint.h",
            "rc2dgi_ctx.h", "rc2dgi_tuning.h", "rc2dgi_present.h", "rc2dgi_texel.h", "rc2dgi_query.h", "rc2dgi_reduce.h",
            "rc2dgi_present_dev.h", "rc2dgi_tone.h", "rc2dgi_hist.h", "rc2dgi_read.h", "rc2dgi_rects.h",
            "rc2dgi_rectplan.h", "rc2dgi_accessory.h", "rc2dgi_write.h", "rc2dgi_paint_raster.h", "rc2dgi_sprites.h",
            "rc2dgi_sprites_tile.h", "rc2dgi_sprites_xf.h", "rc2dgi_paint_setup.h", "rc2dgi_shapes.h",
-           "rc2dgi_tile_test.h", "rc2dgi_tilemap.h", "rc2dgi_tilemap_cell.h"]
+           "rc2dgi_tile_test.h", "rc2dgi_tilemap.h", "rc2dgi_tilemap_cell.h", "rc2dgi_gradients.h", "rc2dgi_gradient_interp.h",
+           "rc2dgi_shapes_setup.h"]
 ARCH = os.environ.get("RC2DGI_OFFLOAD_ARCH", "gfx950")
 
 # -ffp-contract=off: each a*b+c in the kernels is two IEEE roundings, exactly as the GLSL

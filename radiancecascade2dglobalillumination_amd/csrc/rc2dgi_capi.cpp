@@ -2,6 +2,7 @@
 // timing and the tuning entry points.  The frame itself: rc2dgi_frame.cpp; shards: rc2dgi_group.cpp.
 #include "rc2dgi_ctx.h"
 #include "rc2dgi_read.h"
+#include "rc2dgi_gradients.h"
 #include "rc2dgi_shapes.h"
 #include "rc2dgi_sprites_xf.h"
 #include "rc2dgi_tilemap.h"
@@ -290,6 +291,15 @@ int rc2dgi_shapes_device(rc2dgi_ctx *c, int which, const unsigned char *clear_rg
   static_assert(offsetof(rc2dgi_shape, v) == 4 && offsetof(rc2dgi_shape, r) == 28, "a shape is eight 32-bit words");
   return paint_list_call<rc2dgi_shape, 32>(c, "shapes_device", shapes_device, which, clear_rgba, shapes_dev, n,
                                            count_dev, status_dev);
+}
+
+int rc2dgi_gradients_device(rc2dgi_ctx *c, int which, const unsigned char *clear_rgba, const void *grads_dev, int n,
+                            const void *count_dev, void *status_dev) {
+  static_assert(offsetof(rc2dgi_gradient, v) == 4 && offsetof(rc2dgi_gradient, c) == 28 &&
+                    offsetof(rc2dgi_gradient, gain) == 44,
+                "a gradient is twelve 32-bit words");
+  return paint_list_call<rc2dgi_gradient, 48>(c, "gradients_device", gradients_device, which, clear_rgba, grads_dev, n,
+                                              count_dev, status_dev);
 }
 
 int rc2dgi_paint_device_limits(const rc2dgi_config *cfg, int *batch_prims, long long *work_bytes) {

@@ -8,6 +8,7 @@
 
 #include <climits>
 
+#include "rc2dgi_gradient_interp.h"
 #include "rc2dgi_paint_raster.h"
 
 namespace rc2dgi {
@@ -45,8 +46,13 @@ struct PaintAcc {
   long long mnx, mny, mxx, mxy;
 };
 
-// one triangle of paint_prims' loop: dropped when its area is zero, made counter-clockwise, its three edges
-__device__ __forceinline__ void paint_dev_emit(PaintAcc &A, PaintSnap s0, PaintSnap s1, PaintSnap s2) {
+// one triangle of paint_prims' loop: dropped when its area is zero, made counter-clockwise, its three edges.  kTag
+// (rc2dgi_gradients_device): q0, q1, q2 are the colours of s0, s1, s2 as the caller lists them; they go into the
+// record's pad words in that order, with kGradSwapped in `incl` when the swap exchanged s1 and s2
+// (grad_tag, rc2dgi_gradient_interp.h).  Without kTag the pad words are zero, as ever.
+template <bool kTag>
+__device__ __forceinline__ void paint_dev_emit_t(PaintAcc &A, PaintSnap s0, PaintSnap s1, PaintSnap s2, unsigned q0,
+                                                 unsigned q1, unsigned q2) {
   const long long area = (s1.x - s0.x) * (s2.y - s0.y) - (s2.x - s0.x) * (s1.y - s0.y);
   if (area == 0) return;
   if (area < 0) {
@@ -67,7 +73,12 @@ __device__ __forceinline__ void paint_dev_emit(PaintAcc &A, PaintSnap s0, PaintS
     A.mnx = min(A.mnx, a.x); A.mxx = max(A.mxx, a.x);
     A.mny = min(A.mny, a.y); A.mxy = max(A.mxy, a.y);
   }
+  if (kTag) grad_tag(tri, area < 0, q0, q1, q2);
   A.out[A.nt++] = tri;
+}
+
+__device__ __forceinline__ void paint_dev_emit(PaintAcc &A, PaintSnap s0, PaintSnap s1, PaintSnap s2) {
+  paint_dev_emit_t<false>(A, s0, s1, s2, 0u, 0u, 0u);
 }
 
 }  // namespace rc2dgi

@@ -14,4 +14,10 @@ hipError_t shapes_device(float4 *dst, int W, int H, int pitch, bool u8, const un
                          const void *shapes_dev, int n, const void *count_dev, void *status_dev, PaintDevBuffers &buf,
                          hipStream_t st);
 
+// k_shapes_bin over the nb records of the batch at `base`, as shapes_device launches it: prims / tris are the batch's
+// PaintPrim and PaintTri records.  rc2dgi_gradients_device (rc2dgi_gradients.hip) runs it unchanged on records of its
+// own set-up.
+void shapes_enqueue_bin(const void *prims, const void *tris, int n, const int *count_dev, int base, int nb,
+                        const PaintDevPlan &plan, unsigned *masks, hipStream_t st);
+
 }  // namespace rc2dgi

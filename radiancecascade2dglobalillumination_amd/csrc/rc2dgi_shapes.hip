@@ -1,7 +1,8 @@
 // rc2dgi_shapes.hip -- rc2dgi_shapes_device: a device-resident list of rectangles, circles, triangles, thick lines and
 // ellipses painted into an input texture.  rc2dgi_paint_device's sequence of kernels per batch on the
 // same working memory, with a set-up and a binning pass of its own:
-//   k_shapes_setup      one lane a shape: the eight words, the refusal test of its kind (a refused shape gets no
+//   k_shapes_setup      one lane a shape (shapes_setup_record, rc2dgi_shapes_setup.h, the text rc2dgi_gradients.hip
+//                       shares): the eight words, the refusal test of its kind (a refused shape gets no
 //                       triangles and is counted), the kind's vertex list in the header's float operations, then
 //                       paint_dev_window / paint_dev_emit (rc2dgi_paint_setup.h) into the PaintPrim / PaintTri records
 //                       k_paint_dev_raster reads, 36 triangle slots a shape.  RECT and CIRCLE are k_paint_dev_setup's
@@ -21,6 +22,7 @@
 #include "rc2dgi_device.h"
 #include "rc2dgi_paint_raster.h"
 #include "rc2dgi_paint_setup.h"
+#include "rc2dgi_shapes_setup.h"
 #include "rc2dgi_tile_test.h"
 
 #include <algorithm>
@@ -33,92 +35,7 @@ __global__ __launch_bounds__(256) void k_shapes_setup(const unsigned *__restrict
                                                       const int *__restrict__ count_dev, int base, int batch,
                                                       PaintPrim *__restrict__ prims, PaintTri *__restrict__ tris,
                                                       unsigned *__restrict__ counters, PaintXform xf, PaintCircle tab) {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  const int mb = paint_dev_batch(count_dev, n, base, batch);
-  bool refused = false;
-  if (k < mb) {  // (base + k < m <= n: inside the list)
-    const unsigned *q = list + (size_t)(base + k) * 8;
-    const int kind = (int)q[0];
-    const bool rect = kind == RC2DGI_SHAPE_RECT, circle = kind == RC2DGI_SHAPE_CIRCLE,
-               tri = kind == RC2DGI_SHAPE_TRIANGLE, line = kind == RC2DGI_SHAPE_LINE,
-               ellipse = kind == RC2DGI_SHAPE_ELLIPSE;
-    // the words the kind names, no others: 4, 3, 6, 5, 4 of v[]; none for an unknown kind
-    const int nv = rect || ellipse ? 4 : circle ? 3 : tri ? 6 : line ? 5 : 0;
-    float v[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) v[i] = i < nv ? __uint_as_float(q[1 + i]) : 0.0f;
-    bool ok = nv != 0;
-    if (rect || circle) {  // rc2dgi_paint's test, term for term (k_paint_dev_setup)
-      const float lim = 4194304.0f;  // 2^22 pixels
-      ok = fabsf(v[0]) < lim && fabsf(v[1]) < lim && fabsf(v[2]) < lim;
-      if (rect)
-        ok = ok && fabsf(v[3]) < lim && fabsf(__fadd_rn(v[0], v[2])) < lim && fabsf(__fadd_rn(v[1], v[3])) < lim;
-      else
-        ok = ok && __fadd_rn(fabsf(v[0]), fabsf(v[2])) < lim && __fadd_rn(fabsf(v[1]), fabsf(v[2])) < lim;
-    } else {  // every value read is below 2^20 in magnitude (false for a NaN and for an infinity)
-#pragma unroll
-      for (int i = 0; i < 6; ++i) ok = ok && (i >= nv || fabsf(v[i]) < 0x1p20f);
-    }
-    refused = !ok;
-    PaintPrim pp{};
-    pp.tri0 = k * kPaintDevTris;
-    PaintAcc A{tris + (size_t)k * kPaintDevTris, 0, LLONG_MAX, LLONG_MAX, LLONG_MIN, LLONG_MIN};
-    if (ok && rect) {  // DrawRectanglePro (rotation 0): TL, BL, BR, TR as (0, 1, 2), (0, 2, 3)
-      const float xr = __fadd_rn(v[0], v[2]), yb = __fadd_rn(v[1], v[3]);
-      const PaintSnap tl = paint_dev_window(v[0], v[1], xf), tr = paint_dev_window(xr, v[1], xf),
-                      bl = paint_dev_window(v[0], yb, xf), br = paint_dev_window(xr, yb, xf);
-      paint_dev_emit(A, tl, bl, br);
-      paint_dev_emit(A, tl, br, tr);
-    } else if (ok && (circle || ellipse)) {
-      // the fan (c, T(k + 1), T(k)), k = 0 .. 35, T(k) = (cx + c37[k] * rh, cy + s37[k] * rv), two triangles a step as
-      // k_paint_dev_setup walks DrawCircleSector's 18 quads; a circle is rh = rv = radius, a radius <= 0 being 0.1
-      const float rh = circle ? (v[2] <= 0.0f ? 0.1f : v[2]) : v[2], rv = circle ? rh : v[3];
-      const PaintSnap c = paint_dev_window(v[0], v[1], xf);
-      PaintSnap p0 =
-          paint_dev_window(__fadd_rn(v[0], __fmul_rn(tab.c[0], rh)), __fadd_rn(v[1], __fmul_rn(tab.s[0], rv)), xf);
-#pragma unroll 1
-      for (int s = 0; s < 18; ++s) {
-        const int a = 2 * s;
-        const PaintSnap p1 = paint_dev_window(__fadd_rn(v[0], __fmul_rn(tab.c[a + 1], rh)),
-                                              __fadd_rn(v[1], __fmul_rn(tab.s[a + 1], rv)), xf);
-        const PaintSnap p2 = paint_dev_window(__fadd_rn(v[0], __fmul_rn(tab.c[a + 2], rh)),
-                                              __fadd_rn(v[1], __fmul_rn(tab.s[a + 2], rv)), xf);
-        paint_dev_emit(A, c, p2, p1);
-        paint_dev_emit(A, c, p1, p0);
-        p0 = p2;
-      }
-    } else if (ok && tri) {
-      paint_dev_emit(A, paint_dev_window(v[0], v[1], xf), paint_dev_window(v[2], v[3], xf),
-                     paint_dev_window(v[4], v[5], xf));
-    } else if (ok) {  // DrawLineEx: the quad s0, s1, s2, s3 around the segment, as {s0, s1, s2} and {s1, s2, s3}
-      const float dx = __fadd_rn(v[2], -v[0]), dy = __fadd_rn(v[3], -v[1]), thick = v[4];
-      const float len = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
-      if (len > 0.0f && thick > 0.0f) {
-        const float scale = thick / __fmul_rn(2.0f, len);
-        const float rx = __fmul_rn(-scale, dy), ry = __fmul_rn(scale, dx);
-        const PaintSnap s0 = paint_dev_window(__fadd_rn(v[0], -rx), __fadd_rn(v[1], -ry), xf),
-                        s1 = paint_dev_window(__fadd_rn(v[0], rx), __fadd_rn(v[1], ry), xf),
-                        s2 = paint_dev_window(__fadd_rn(v[2], -rx), __fadd_rn(v[3], -ry), xf),
-                        s3 = paint_dev_window(__fadd_rn(v[2], rx), __fadd_rn(v[3], ry), xf);
-        paint_dev_emit(A, s0, s1, s2);
-        paint_dev_emit(A, s1, s2, s3);
-      }
-    }
-    pp.ntri = A.nt;
-    if (pp.ntri > 0) {  // pixels whose centre 256 i + 128 lies in [min, max], clipped to the target
-      pp.x0 = (int)max(0LL, -paint_dev_floor_div(-(A.mnx - 128), 256));
-      pp.x1 = (int)min((long long)xf.W - 1, paint_dev_floor_div(A.mxx - 128, 256));
-      pp.y0 = (int)max(0LL, -paint_dev_floor_div(-(A.mny - 128), 256));
-      pp.y1 = (int)min((long long)xf.H - 1, paint_dev_floor_div(A.mxy - 128, 256));
-      if (pp.x0 > pp.x1 || pp.y0 > pp.y1) pp.ntri = 0;
-    }
-    const unsigned rgba = q[7];
-    pp.color = make_float4(__fmul_rn((float)(rgba & 255u), kInv255), __fmul_rn((float)((rgba >> 8) & 255u), kInv255),
-                           __fmul_rn((float)((rgba >> 16) & 255u), kInv255), __fmul_rn((float)(rgba >> 24), kInv255));
-    prims[k] = pp;
-  }
-  const unsigned long long b = __ballot(refused);  // integer adds: the sum is the same in any order
-  if (b != 0 && (threadIdx.x & 63) == 0) atomicAdd(&counters[0], (unsigned)__popcll(b));
+  shapes_setup_record<8, false>(list, n, count_dev, base, batch, prims, tris, counters, xf, tab);
 }
 
 __global__ __launch_bounds__(256) void k_shapes_bin(const PaintPrim *__restrict__ prims,
@@ -176,6 +93,14 @@ __global__ __launch_bounds__(256) void k_shapes_bin(const PaintPrim *__restrict_
 
 }  // namespace
 
+void shapes_enqueue_bin(const void *prims, const void *tris, int n, const int *count_dev, int base, int nb,
+                        const PaintDevPlan &plan, unsigned *masks, hipStream_t st) {
+  int th_shift = 0;
+  while ((1 << th_shift) < plan.tile_h) ++th_shift;
+  hipLaunchKernelGGL(k_shapes_bin, dim3((nb + 3) / 4), dim3(256), 0, st, static_cast<const PaintPrim *>(prims),
+                     static_cast<const PaintTri *>(tris), n, count_dev, base, plan.batch, masks, plan.tiles_x, th_shift);
+}
+
 hipError_t shapes_device(float4 *dst, int W, int H, int pitch, bool u8, const unsigned char *clear,
                          const void *shapes_dev, int n, const void *count_dev, void *status_dev, PaintDevBuffers &buf,
                          hipStream_t st) {
@@ -197,8 +122,6 @@ hipError_t shapes_device(float4 *dst, int W, int H, int pitch, bool u8, const un
   // to_window's constants (rc2dgi_paint.hip), evaluated here as it evaluates them
   const PaintXform xf{2.0f / (float)W, 2.0f / (float)(-H), (float)W * 0.5f, (float)H * 0.5f, W, H};
   const float4 cl = paint_dev_clear(clear, u8);
-  int th_shift = 0;
-  while ((1 << th_shift) < plan.tile_h) ++th_shift;
   // the batches follow each other on the stream: batch b + 1 blends over what batch b left, so the draw order holds
   const int batches = n == 0 ? (clear ? 1 : 0) : (n + plan.batch - 1) / plan.batch;
   for (int b = 0; b < batches; ++b) {
@@ -207,8 +130,7 @@ hipError_t shapes_device(float4 *dst, int W, int H, int pitch, bool u8, const un
       hipLaunchKernelGGL(k_shapes_setup, dim3((nb + 255) / 256), dim3(256), 0, st,
                          static_cast<const unsigned *>(shapes_dev), n, cnt, base, plan.batch, prims, tris, counters, xf,
                          tab);
-      hipLaunchKernelGGL(k_shapes_bin, dim3((nb + 3) / 4), dim3(256), 0, st, static_cast<const PaintPrim *>(prims),
-                         static_cast<const PaintTri *>(tris), n, cnt, base, plan.batch, masks, plan.tiles_x, th_shift);
+      shapes_enqueue_bin(prims, tris, n, cnt, base, nb, plan, masks, st);
     }
     paint_dev_enqueue_raster(dst, W, H, pitch, u8, clear && b == 0, cl, prims, tris, masks, n, cnt, base, plan, st);
     e = hipGetLastError();

@@ -94,6 +94,17 @@ class Shape(ctypes.Structure):
 SHAPE_RECT, SHAPE_CIRCLE, SHAPE_TRIANGLE, SHAPE_LINE, SHAPE_ELLIPSE = 0, 1, 2, 3, 4
 
 
+class Gradient(ctypes.Structure):
+    """rc2dgi_gradient (48 bytes): kind GRAD_*, Shape's six floats by kind, four raylib Colors (TRIANGLE c[0..2] a
+    vertex; RECT c[0..3] = TL, BL, BR, TR; CIRCLE and ELLIPSE c[0] the centre, c[1] the rim; LINE c[0] the (x0, y0) end,
+    c[1] the other) and the gain that multiplies r, g, b after the interpolation."""
+    _fields_ = [("kind", ctypes.c_int), ("v", ctypes.c_float * 6), ("c", (ctypes.c_ubyte * 4) * 4),
+                ("gain", ctypes.c_float)]
+
+
+GRAD_RECT, GRAD_CIRCLE, GRAD_TRIANGLE, GRAD_LINE, GRAD_ELLIPSE = 0, 1, 2, 3, 4
+
+
 class Tilemap(ctypes.Structure):
     """rc2dgi_tilemap (56 bytes): a rows x cols grid of 32-bit cell words on the device (Tiled's global tile ids, 0 an
     empty cell, bit 31 / 30 the horizontal / vertical flip), cells of tile_w x tile_h pixels with cell (0, 0) at (ox, oy)
@@ -343,6 +354,8 @@ def load_library(path: Optional[str] = None):
                                    ctypes.c_int, vp, vp], ctypes.c_int),
         "rc2dgi_sprites_xf_device": ([vp, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(Atlas), vp,
                                       ctypes.c_int, vp, vp], ctypes.c_int),
+        "rc2dgi_gradients_device": ([vp, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), vp, ctypes.c_int, vp, vp],
+                                    ctypes.c_int),
         "rc2dgi_tilemap_device": ([vp, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(Atlas),
                                    ctypes.POINTER(Tilemap), vp], ctypes.c_int),
     }
@@ -545,6 +558,16 @@ class RC2DGI:
         paint_device list into one); clear, count and status as for paint_device.  A shape the header's rule refuses
         draws nothing and is counted in status[1].  Keep the tensors alive until sync()."""
         self._paint_list("shapes_device", self._L.rc2dgi_shapes_device, 8, "shapes", which, shapes, clear, count, status)
+
+    def gradients_device(self, which, grads, clear=None, count=None, status=None) -> None:
+        """The five shapes with a colour a vertex and an HDR gain, from a list in device memory, painted in list order
+        (rc2dgi_gradients_device): nothing waits.  grads: a contiguous torch.int32 (n, 12) tensor on this context's
+        GPU, a row the twelve words of rc2dgi_gradient (pack_gradients makes one, soft_lights makes round lights that
+        fade to nothing at the rim, gradients_from_shapes turns a shapes_device list into one); clear, count and status
+        as for paint_device.  A record the header's rule refuses draws nothing and is counted in status[1].  Keep the
+        tensors alive until sync()."""
+        self._paint_list("gradients_device", self._L.rc2dgi_gradients_device, 12, "grads", which, grads, clear, count,
+                         status)
 
     def _paint_list(self, call, fn, words, what, which, recs, clear, count, status) -> None:
         w = RT[which] if isinstance(which, str) else int(which)
@@ -1129,6 +1152,63 @@ def shapes_from_prims(prims):
     if prims.dim() != 2 or prims.shape[1] != 6 or prims.dtype != torch.int32:
         raise ValueError(f"shapes_from_prims: prims is (n, 6) int32, got {tuple(prims.shape)} {prims.dtype}")
     return torch.cat([prims[:, :5], torch.zeros_like(prims[:, :2]), prims[:, 5:6]], dim=1).contiguous()
+
+
+def pack_gradients(kind, v6, colors, gain=None):
+    """The (n, 12) int32 tensor RC2DGI.gradients_device takes, with torch ops alone on the inputs' device (nothing
+    waits): kind (n,) of any integer dtype (GRAD_*), v6 (n, 6) float32 (pack_shapes' v6), colors (n, 4, 4) uint8 (four
+    r, g, b, a colours a record; those the kind does not name are not read), gain (n,) float32, None: 1.  The float
+    bits are reinterpreted; colour k goes little-endian into word 7 + k, as rc2dgi_gradient lays them out."""
+    import torch
+
+    n = int(kind.shape[0])
+    if tuple(kind.shape) != (n,) or kind.dtype.is_floating_point or kind.dtype == torch.bool:
+        raise ValueError(f"pack_gradients: kind is (n,) of an integer dtype, got {tuple(kind.shape)} {kind.dtype}")
+    if tuple(v6.shape) != (n, 6) or v6.dtype != torch.float32:
+        raise ValueError(f"pack_gradients: v6 is ({n}, 6) float32, got {tuple(v6.shape)} {v6.dtype}")
+    if tuple(colors.shape) != (n, 4, 4) or colors.dtype != torch.uint8:
+        raise ValueError(f"pack_gradients: colors is ({n}, 4, 4) uint8, got {tuple(colors.shape)} {colors.dtype}")
+    if gain is None:
+        gain = torch.ones(n, dtype=torch.float32, device=v6.device)
+    if tuple(gain.shape) != (n,) or gain.dtype != torch.float32:
+        raise ValueError(f"pack_gradients: gain is ({n},) float32, got {tuple(gain.shape)} {gain.dtype}")
+    return torch.cat([kind.reshape(n, 1).to(torch.int32), v6.contiguous().view(torch.int32),
+                      colors.contiguous().view(torch.int32).reshape(n, 4),
+                      gain.contiguous().view(torch.int32).reshape(n, 1)], dim=1)
+
+
+def gradients_from_shapes(shapes):
+    """The (n, 12) gradients_device list that paints what the (n, 8) shapes_device list `shapes` paints: words 0 .. 6
+    as they are, the colour of word 7 in all four colour words, gain 1.0 (GRAD_* are SHAPE_*'s values).  Torch ops
+    alone on the input's device."""
+    import torch
+
+    if shapes.dim() != 2 or shapes.shape[1] != 8 or shapes.dtype != torch.int32:
+        raise ValueError(f"gradients_from_shapes: shapes is (n, 8) int32, got {tuple(shapes.shape)} {shapes.dtype}")
+    one = torch.full_like(shapes[:, :1], 0x3F800000)  # the bits of 1.0f
+    return torch.cat([shapes[:, :7], shapes[:, 7:8].expand(-1, 4), one], dim=1).contiguous()
+
+
+def soft_lights(xy, radius, rgb, gain=None):
+    """The (n, 12) gradients_device list of n round lights, bright at the centre and fading to nothing at the rim
+    (raylib's DrawCircleGradient(centre, radius, (rgb, 255), (rgb, 0))): GRAD_CIRCLE records with c[0] = (rgb, 255) and
+    c[1] = (rgb, 0).  xy (n, 2) float32 the centres, radius (n,) float32, rgb (n, 3) uint8, gain (n,) float32 (None: 1)
+    the HDR factor on r, g, b.  Torch ops alone on the inputs' device: a particle system kept as tensors becomes lights
+    without leaving it."""
+    import torch
+
+    if xy.dim() != 2 or xy.shape[1] != 2 or xy.dtype != torch.float32:
+        raise ValueError(f"soft_lights: xy is (n, 2) float32, got {tuple(xy.shape)} {xy.dtype}")
+    n = int(xy.shape[0])
+    if tuple(radius.shape) != (n,) or radius.dtype != torch.float32:
+        raise ValueError(f"soft_lights: radius is ({n},) float32, got {tuple(radius.shape)} {radius.dtype}")
+    if tuple(rgb.shape) != (n, 3) or rgb.dtype != torch.uint8:
+        raise ValueError(f"soft_lights: rgb is ({n}, 3) uint8, got {tuple(rgb.shape)} {rgb.dtype}")
+    v6 = torch.cat([xy, radius.reshape(n, 1), torch.zeros((n, 3), dtype=torch.float32, device=xy.device)], dim=1)
+    alpha = torch.tensor([255, 0, 0, 0], dtype=torch.uint8, device=xy.device).reshape(1, 4, 1).expand(n, 4, 1)
+    colors = torch.cat([rgb.reshape(n, 1, 3).expand(n, 4, 3), alpha], dim=2)
+    kind = torch.full((n,), GRAD_CIRCLE, dtype=torch.int32, device=xy.device)
+    return pack_gradients(kind, v6, colors, gain)
 
 
 def pack_sprites(src_xywh, dst_xy, tint=None, flags=None):
